@@ -11,11 +11,18 @@ generated on the device (nothing crosses PCIe in the timed region).
 The headline decodes in fp64, the reference's own arithmetic
 (decodeMinSum.cpp:39-40,410-476 hold every message in `double`), with the
 fast fp64 row kernel whose decisions equal the reference's bit for bit
-(tests/test_rows_fast.py). The fp32 throughput path is timed after it over
-the same steps and reported under "f32".
+(tests/test_rows_fast.py).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
+
+A plain run does what the headline figure needs and no more: set up, W warm-up
+steps, K timed steps, the result line. `--dump-outputs DIR` also writes what the
+last timed step returned to its caller (dump_outputs below). `--full` adds every
+leg that takes runs of its own: the fp32 throughput path timed over the same
+steps (reported under "f32"), the live HBM-traffic passes, the CPU baseline and
+the FER comparison with the reference; --no-secondary, --no-cpu-baseline and
+--live-pmc off take single legs out of a --full run.
 
 `--gpus N` without torchrun's environment starts torchrun itself (a child
 process, before anything touches the GPU) and exits with its status.
@@ -37,15 +44,16 @@ edges of its row slots included; the library reports its slot degrees) and
 `padded` (every row slot at the padded degree, the rounds 2-4 model). The SURVEY §8(d) flooding HBM
 message model (16E+4N bytes per codeword-iteration) is kept as `hbm_model`;
 it does not bound this kernel (messages never leave LDS), so its "fraction"
-exceeds 1. `traffic` = HBM bytes per launch of the headline kernel, measured
+exceeds 1. `traffic` (--full) = HBM bytes per launch of the headline kernel, measured
 live after the timed steps: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE;
 separate passes, MI355X_MICROARCH's counter limits) over a child run of this
 same workload (1 warm-up + 1 step), FETCH_SIZE doubled (the guide's gfx950
 correction); `traffic_gbs` = those bytes over this run's average launch time,
 against the 8 TB/s HBM peak. --live-pmc off (or running under a profiler)
-falls back to the committed PMC summary (profiles/traffic_latest.json).
+falls back to the committed PMC summary (profiles/traffic_latest.json), also
+only with --full: a plain run reports `traffic` and its companions as null.
 
-cpu_baseline: the reference's own decodeNMS (oracle/_ref, compiled from the
+cpu_baseline (--full): the reference's own decodeNMS (oracle/_ref, compiled from the
 unmodified sources) on this box's host cores, same code/variant/T/SNR.
 """
 from __future__ import annotations
@@ -96,7 +104,13 @@ def parse(argv=None):
     p.add_argument("--T", type=int, default=50)
     p.add_argument("--alpha", type=float, default=1.25)
     p.add_argument("--precision", choices=["f32", "f64"], default="f64")
-    p.add_argument("--no-secondary", action="store_true", help="skip the fp32 run after the fp64 headline")
+    p.add_argument("--full", action="store_true",
+                   help="also run the legs beyond the headline: fp32 secondary, live HBM traffic (rocprofv3 "
+                        "child runs), CPU baseline, FER comparison with the reference")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the last timed step of the headline run returned as DIR/<name>.npy (see "
+                        "dump_outputs); the fp32 leg of a --full run is not dumped")
+    p.add_argument("--no-secondary", action="store_true", help="--full: skip the fp32 run after the fp64 headline")
     p.add_argument("--seed", type=int, default=20261015)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-procs", type=int, default=0, help="0 = the box's CPU share (see cpu_share())")
@@ -368,6 +382,23 @@ def lds_models_alt(si: dict) -> dict:
             "padded": {"cycles_per_group_iter": rows * si["dc"] / 64 * (rd + wr) + bit}}
 
 
+COUNT_FIELDS = ("bit_err", "frame_err", "uncoded_bit_err", "frames", "iters", "syndrome_fail")
+
+
+def dump_outputs(out_dir: str, frames_dev, counts: np.ndarray, suffix: str = "") -> None:
+    """--dump-outputs: what a caller of the timed path (Context.sim_launch + read_counts)
+    holds after the last timed step, as float64 .npy files (the int32 / int64 counters
+    convert exactly):
+      frames.npy  [batch, 4]  the last step's per-frame record (native.FRAME_DTYPE: bit_err,
+                              uncoded_bit_err, syndrome_fail, iters), 2 MiB at the default batch
+      counts.npy  [6]         the context's counters over the timed steps (COUNT_FIELDS order)
+    The channel noise is Philox keyed by (--seed, global frame index), so the same
+    arguments give the same inputs, and these files can be compared between builds."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"frames{suffix}.npy"), frames_dev.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, f"counts{suffix}.npy"), np.asarray(counts[:len(COUNT_FIELDS)], dtype=np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -418,7 +449,7 @@ def main():
     ctx.set_stream(stream.cuda_stream)
     frames_dev = torch.empty((B, 4), dtype=torch.int32, device="cuda")
 
-    def run(precision: str, stream_id: int) -> dict:
+    def run(precision: str, stream_id: int, dump_dir: Optional[str] = None) -> dict:
         cfg = native.DecoderConfig(variant=native.NMS, alpha=args.alpha, T=args.T,
                                    precision=native.F64 if precision == "f64" else native.F32)
 
@@ -451,6 +482,8 @@ def main():
         kern_ms = [a.elapsed_time(b) for a, b in ev]
         redo = ctx.redo_count()
         cnt = ctx.read_counts(reset=True).as_array()
+        if dump_dir:   # this rank's own outputs, outside the timed region
+            dump_outputs(dump_dir, frames_dev, cnt, f"_rank{rank}" if world > 1 else "")
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         c = torch.from_numpy(np.append(cnt, redo)).to(coll_dev)
         if distributed:
@@ -463,9 +496,9 @@ def main():
         return {"cfg": cfg, "elapsed": elapsed, "kern_ms": kern_ms, "tot": tot,
                 "value": frames_total * g.N / elapsed / 1e6}
 
-    head = run(args.precision, 0)
+    head = run(args.precision, 0, args.dump_outputs)
     sec = None
-    if not args.no_secondary and args.precision == "f64":
+    if args.full and not args.no_secondary and args.precision == "f64":
         sec = run("f32", 1)
 
     def roofline(r: dict) -> dict:
@@ -500,11 +533,12 @@ def main():
         rl = roofline(head)
         traffic, traffic_src, traffic_kernel, live = None, None, None, None
         nested = any(k.startswith("ROCPROF") for k in os.environ) or "rocprofiler" in os.environ.get("LD_PRELOAD", "")
-        if args.live_pmc == "auto" and world == 1 and not nested:
+        live_pmc = args.full and args.live_pmc == "auto" and world == 1 and not nested
+        if live_pmc:
             live = live_traffic(args, rl["kernel"])
             if "hbm_bytes_per_launch" in live:
                 traffic, traffic_src, traffic_kernel = live["hbm_bytes_per_launch"], live["source"], live["kernel_pattern"]
-        if traffic is None:   # the committed PMC summary of this round (scripts/profile_round.sh)
+        if args.full and traffic is None:   # the committed PMC summary of this round (scripts/profile_round.sh)
             try:
                 tj = json.load(open(args.traffic_json))
                 tj = tj.get(args.precision, {})
@@ -519,7 +553,7 @@ def main():
         fer = {"ebn0_db": args.ebn0, "frame_err": k_fe, "frames": n_fe, "fer": k_fe / n_fe,
                "ber": float(tot[0]) / (n_fe * g.N), "wilson95": wilson_interval(k_fe, n_fe),
                "redecoded_exact_last_launch": int(tot[6])}
-        ref = reference_fer()
+        ref = reference_fer() if args.full else {}
         if args.ebn0 in ref and args.T == 50 and args.alpha == 1.25:
             kr, nr = ref[args.ebn0]
             fer.update(ref_frame_err=kr, ref_frames=nr, ref_fer=kr / nr,
@@ -545,6 +579,7 @@ def main():
             "fer": fer,
             "kernel_info": ctx.kernel_info(head["cfg"]),
             "collective_backend": dist.get_backend() if distributed else None,
+            "full": args.full, "dumped_outputs": args.dump_outputs,
         }
         if sec is not None:
             rs = roofline(sec)
@@ -552,12 +587,12 @@ def main():
                           "avg_kernel_ms": rs["avg_kernel_ms"], "kernel": rs["kernel"],
                           "lds_frac": rs.get("frac"), "frame_err": int(sec["tot"][1]), "frames": int(sec["tot"][3]),
                           "note": "fp32 throughput path (same workload, Philox stream 1); not the reference's precision"}
-            if args.live_pmc == "auto" and world == 1 and not nested:
+            if live_pmc:
                 # the fp32 kernel's HBM bytes, measured the same way as the headline's
                 lt = live_traffic(args, rs["kernel"], "f32")
                 out["f32"]["traffic"] = lt.get("hbm_bytes_per_launch")
                 out["f32"]["traffic_detail"] = {k: v for k, v in lt.items() if k != "hbm_bytes_per_launch"}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             procs = args.cpu_procs or cpu_share()
             try:
                 out["cpu_baseline"] = cpu_baseline(alist, args.T, args.alpha, args.ebn0, procs)

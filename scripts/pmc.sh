@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 OUT=gpurun_out/${RUN_TAG:-pmc}
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-ARGS="--steps ${PMC_STEPS:-2} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
+ARGS="--full --steps ${PMC_STEPS:-2} --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-}"
 if [ "${LIST:-0}" = 1 ]; then timeout -k 10 120 rocprofv3 -L > "$OUT/counters.txt" 2>&1; fi
 i=0
 for set in "${@}"; do

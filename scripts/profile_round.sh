@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 OUT=gpurun_out/${RUN_TAG:-prof}
 mkdir -p "$OUT"
-ARGS="--steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-}"
+ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline ${BENCH_ARGS:-}"
 run() { local name=$1; shift; echo "=== $name"; timeout -k 10 300 "$@" > "$OUT/$name.log" 2>&1; local rc=$?; echo "rc=$rc"; tail -1 "$OUT/$name.log" | cut -c1-400; [ $rc -eq 0 ] || exit $rc; }
 run stats rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o run --output-format csv -- python3 bench.py $ARGS
 run fetch rocprofv3 --pmc FETCH_SIZE -d "$OUT/fetch" -o pmc --output-format csv -- python3 bench.py $ARGS

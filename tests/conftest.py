@@ -10,7 +10,10 @@ if ROOT not in sys.path:
 
 GOLD = os.path.join(ROOT, "tests", "golden")
 CODES = os.path.join(GOLD, "codes")
-REFERENCE = "/root/reference/C_implementations"
+# the reference's own codes/802.11n/*.alist (Z=27, transposed and unpadded), stored verbatim
+REF_80211N = os.path.join(CODES, "reference_80211n")
+# the data files of the reference's SystemC/NB-LDPC/codes/*/ (binary-format alists, .pchk / .gen, GF(2)), each .xz
+REF_NB = os.path.join(CODES, "reference_nb")
 
 
 def pytest_configure(config):

@@ -7,7 +7,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import REFERENCE, ROOT, code_path
+from conftest import REF_80211N, ROOT, code_path
 from ldpcsimulation_amd import codes, native
 
 
@@ -64,12 +64,11 @@ def test_graph_validation_rejects_inconsistent_views():
         native.Graph.from_lists(2, 1, [[1, 1], []], [[1, 1]])
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present")
 def test_broken_reference_80211n_file_is_an_error_not_a_crash():
     """codes/802.11n/802.11n.alist is transposed and unpadded; the reference loader
     reads garbage and decodeMinSum segfaults. Ours reports it."""
     with pytest.raises(native.LdpcError) as e:
-        native.Graph.from_alist(os.path.join(REFERENCE, "codes", "802.11n", "802.11n.alist"))
+        native.Graph.from_alist(os.path.join(REF_80211N, "802.11n.alist"))
     assert e.value.code == -6
 
 

@@ -4,6 +4,8 @@ import importlib.util
 import os
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -27,6 +29,69 @@ def test_driver_flags(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "3"])
     a = b.parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 3)
+
+
+def test_plain_run_is_the_default_and_full_is_opt_in(monkeypatch):
+    """A plain run times the headline only; --full switches the other legs on, and the
+    flags that take single legs out of a full run still parse without it (scripts pass them)."""
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "1"])
+    a = b.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 7
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-secondary", "--no-cpu-baseline", "--live-pmc", "off",
+                                      "--dump-outputs", "somewhere"])
+    a = b.parse()
+    assert a.full and a.no_secondary and a.no_cpu_baseline and a.live_pmc == "off" and a.dump_outputs == "somewhere"
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    """--dump-outputs: frames.npy is the per-frame record of the last step, counts.npy the
+    context's six counters, both float64 and exact for the integer counters."""
+    import numpy as np
+    import torch
+    b = _bench()
+    frames = torch.arange(5 * 4, dtype=torch.int32).reshape(5, 4)
+    counts = np.array([11, 2, 30, 5, 250, 3, 99], dtype=np.int64)    # a seventh value (bench's redo count) is not a counter
+    out = tmp_path / "new" / "dir"
+    b.dump_outputs(str(out), frames, counts)
+    f, c = np.load(out / "frames.npy"), np.load(out / "counts.npy")
+    assert f.dtype == np.float64 and f.shape == (5, 4) and np.array_equal(f, frames.numpy())
+    assert c.dtype == np.float64 and c.tolist() == [11, 2, 30, 5, 250, 3]
+    assert len(b.COUNT_FIELDS) == 6
+    b.dump_outputs(str(out), frames, counts, "_rank1")
+    assert sorted(p.name for p in out.iterdir()) == ["counts.npy", "counts_rank1.npy", "frames.npy", "frames_rank1.npy"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_and_dumped_outputs(tmp_path, gpu_ctx_factory):
+    """A plain run (no --full) prints the headline line without the legs that take runs of
+    their own, and --dump-outputs holds what sim_launch returned in the last timed step:
+    the same frames an independent sim_batch call over that step's frame indices gives."""
+    import json
+    import subprocess
+    import numpy as np
+    from ldpcsimulation_amd import native
+    B, steps, warmup, seed = 4096, 2, 1, 77
+    p = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--batch", str(B), "--seed", str(seed), "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["unit"] == "Mbit/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["full"] is False and "f32" not in line and "cpu_baseline" not in line
+    assert line["roofline"]["traffic"] is None and "z_vs_reference" not in line["fer"]
+    assert line["fer"]["frames"] == steps * B
+    f, c = np.load(tmp_path / "out" / "frames.npy"), np.load(tmp_path / "out" / "counts.npy")
+    assert f.shape == (B, 4) and f.dtype == np.float64
+    assert c[3] == steps * B and c[1] == line["fer"]["frame_err"]
+    ctx = gpu_ctx_factory("80211n_1944_r12.alist", B)
+    cfg = native.DecoderConfig(variant=native.NMS, alpha=1.25, T=50, precision=native.F64)
+    fr, _ = ctx.sim_batch(1.5, 0.5, cfg, seed, 0, (warmup + steps - 1) * B, B)
+    want = np.stack([fr[k] for k in ("bit_err", "uncoded_bit_err", "syndrome_fail", "iters")], axis=1)
+    assert np.array_equal(f, want)
 
 
 def test_reference_fer_table_matches_survey():

@@ -5,7 +5,7 @@ import os
 
 import pytest
 
-from conftest import REFERENCE, code_path
+from conftest import REF_80211N, code_path
 from ldpcsimulation_amd import codes
 
 
@@ -29,11 +29,10 @@ def test_committed_fixture_is_the_generated_code():
         assert hashlib.md5(f.read()).hexdigest() == codes.MD5_80211N_1944
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present")
 @pytest.mark.parametrize("fname", ["802.11n.alist", "ldpc_802.11n.alist"])
 def test_z27_left_shift_matches_reference_file(fname):
     """The reference's 802.11n files hold the Z=27 R1/2 code with left-shift circulants."""
-    R = codes.read_alist_tolerant(os.path.join(REFERENCE, "codes", "802.11n", fname), transposed=True)
+    R = codes.read_alist_tolerant(os.path.join(REF_80211N, fname), transposed=True)
     H = codes.ieee80211n_r12(27, "left")
     assert (R.N, R.M) == (648, 324)
     assert R.rows == H.rows
