@@ -12,7 +12,9 @@ HIPFLAGS  = --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -Iincl
 CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 
 LIB       = $(LIBDIR)/libldpc_hip.so
-OBJS      = $(LIBDIR)/obj/kernels.o $(LIBDIR)/obj/rows_fast.o $(LIBDIR)/obj/rows_pp.o $(LIBDIR)/obj/gdbf.o $(LIBDIR)/obj/bp.o $(LIBDIR)/obj/nb.o $(LIBDIR)/obj/nb_api.o $(LIBDIR)/obj/nb_graph.o $(LIBDIR)/obj/api.o $(LIBDIR)/obj/graph.o
+# the min-sum kernel families that `make variant` rebuilds (one translation unit each)
+MINSUM    = kernels rows flood layered
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
             $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF
@@ -52,25 +54,19 @@ PPSCHED ?= -mllvm -amdgpu-sched-strategy=max-memory-clause
 # rows 21.7 -> 21.3 ms; flooding and BP equal). Explicit vector types (the fp32 row
 # kernel's pairs) are not affected.
 NOSLP = -fno-slp-vectorize
-$(LIBDIR)/obj/kernels.o: $(CSRC)/kernels.hip $(CSRC)/kernels.h $(CSRC)/device_common.h $(CSRC)/minsum_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(NOSLP) -c -o $@ $<
-$(LIBDIR)/obj/rows_fast.o: $(CSRC)/rows_fast.hip $(CSRC)/fast64.h $(CSRC)/kernels.h $(CSRC)/device_common.h $(CSRC)/minsum_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) -c -o $@ $<
-$(LIBDIR)/obj/rows_pp.o: $(CSRC)/rows_pp.hip $(CSRC)/fast64.h $(CSRC)/kernels.h $(CSRC)/device_common.h $(CSRC)/minsum_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED) -c -o $@ $<
-$(LIBDIR)/obj/gdbf.o: $(CSRC)/gdbf.hip $(CSRC)/gdbf.h $(CSRC)/kernels.h $(CSRC)/device_common.h $(CSRC)/minsum_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) $(NOSLP) -c -o $@ $<
-$(LIBDIR)/obj/bp.o: $(CSRC)/bp.hip $(CSRC)/bp.h $(CSRC)/bp_math.h $(CSRC)/kernels.h $(CSRC)/device_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(LIBDIR)/obj/nb.o: $(CSRC)/nb.hip $(CSRC)/nb.h $(CSRC)/nb_layout.h $(CSRC)/kernels.h $(CSRC)/device_common.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) $(NOSLP) -c -o $@ $<
-$(LIBDIR)/obj/nb_api.o: $(CSRC)/nb_api.cpp $(CSRC)/nb.h $(CSRC)/nb_layout.h $(CSRC)/nb_graph.h $(CSRC)/kernels.h include/ldpc_hip.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(LIBDIR)/obj/nb_graph.o: $(CSRC)/nb_graph.cpp $(CSRC)/nb_graph.h $(CSRC)/nb_layout.h include/ldpc_hip.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(LIBDIR)/obj/api.o: $(CSRC)/api.cpp $(CSRC)/bp.h $(CSRC)/kernels.h $(CSRC)/gdbf.h $(CSRC)/graph.h include/ldpc_hip.h | $(LIBDIR)/obj
-	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
-$(LIBDIR)/obj/graph.o: $(CSRC)/graph.cpp $(CSRC)/graph.h | $(LIBDIR)/obj
+# Per-file flags beyond HIPFLAGS, by file stem; the product and the checked build read them.
+FLAGS_kernels   = $(KERNFLAGS) $(NOSLP)
+FLAGS_rows      = $(KERNFLAGS) $(NOSLP)
+FLAGS_flood     = $(KERNFLAGS) $(NOSLP)
+FLAGS_layered   = $(KERNFLAGS) $(NOSLP)
+FLAGS_rows_fast = $(KERNFLAGS)
+FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
+FLAGS_gdbf      = $(NOSLP)
+FLAGS_nb        = $(NOSLP)
+HDRS      = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h
+$(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS) | $(LIBDIR)/obj
+	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -c -o $@ $<
+$(LIBDIR)/obj/%.o: $(CSRC)/%.cpp $(HDRS) | $(LIBDIR)/obj
 	$(HIPCC) $(HIPFLAGS) -c -o $@ $<
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(OBJS)
@@ -113,12 +109,15 @@ $(BINDIR)/decodeStochasticNGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BIN
 	g++ $(CXXFLAGS) -D quantizeSamples -D quantizeProbabilities -D weightSyndromes -D saturateSamples -o $@ $< $(CLI_LINK)
 
 # Kernel A/B variants: make variant NAME=x VFLAGS="-DLDPC_..." -> ab/libldpc_hip_x.so
+VAR_STEMS = $(MINSUM) api
 variant:
 	mkdir -p $(VARDIR)/obj_$(NAME)
-	$(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(NOSLP) -DLDPC_AB_BUILD $(VFLAGS) -c -o $(VARDIR)/obj_$(NAME)/kernels.o $(CSRC)/kernels.hip
+	for f in $(MINSUM); do \
+	    $(HIPCC) $(HIPFLAGS) $(KERNFLAGS) $(NOSLP) -DLDPC_AB_BUILD $(VFLAGS) -c -o $(VARDIR)/obj_$(NAME)/$$f.o $(CSRC)/$$f.hip || exit 1; \
+	done
 	$(HIPCC) $(HIPFLAGS) -DLDPC_AB_BUILD $(VFLAGS) -c -o $(VARDIR)/obj_$(NAME)/api.o $(CSRC)/api.cpp
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(VARDIR)/libldpc_hip_$(NAME).so \
-	    $(VARDIR)/obj_$(NAME)/kernels.o $(VARDIR)/obj_$(NAME)/api.o $(LIBDIR)/obj/rows_fast.o $(LIBDIR)/obj/rows_pp.o $(LIBDIR)/obj/gdbf.o $(LIBDIR)/obj/bp.o $(LIBDIR)/obj/nb.o $(LIBDIR)/obj/nb_api.o $(LIBDIR)/obj/nb_graph.o $(LIBDIR)/obj/graph.o
+	    $(patsubst %,$(VARDIR)/obj_$(NAME)/%.o,$(VAR_STEMS)) $(filter-out $(patsubst %,$(LIBDIR)/obj/%.o,$(VAR_STEMS)),$(OBJS))
 
 # Fast row kernel A/B variants: make fastvariant NAME=x VFLAGS="-DLDPC_FAST_..." [FASTSRC=file] -> ab/libldpc_hip_x.so
 FASTSRC ?= $(CSRC)/rows_fast.hip
@@ -170,17 +169,11 @@ bpvariant: $(OBJS)
 CHKDIR    = $(LIBDIR)/checked
 CHKLIB    = $(CHKDIR)/libldpc_hip_checked.so
 CHK_OBJS  = $(patsubst $(LIBDIR)/obj/%.o,$(CHKDIR)/obj/%.o,$(OBJS))
-CHK_HDRS  = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h
-FLAGS_kernels   = $(KERNFLAGS) $(NOSLP)
-FLAGS_rows_fast = $(KERNFLAGS)
-FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
-FLAGS_gdbf      = $(NOSLP)
-FLAGS_nb        = $(NOSLP)
 $(CHKDIR)/obj:
 	mkdir -p $@
-$(CHKDIR)/obj/%.o: $(CSRC)/%.hip $(CHK_HDRS) | $(CHKDIR)/obj
+$(CHKDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS) | $(CHKDIR)/obj
 	$(HIPCC) $(HIPFLAGS) $(FLAGS_$*) -DLDPC_CHECK -c -o $@ $<
-$(CHKDIR)/obj/%.o: $(CSRC)/%.cpp $(CHK_HDRS) | $(CHKDIR)/obj
+$(CHKDIR)/obj/%.o: $(CSRC)/%.cpp $(HDRS) | $(CHKDIR)/obj
 	$(HIPCC) $(HIPFLAGS) -DLDPC_CHECK -c -o $@ $<
 $(CHKLIB): $(CHK_OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $(CHK_OBJS)

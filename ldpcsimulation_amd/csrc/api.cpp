@@ -64,7 +64,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
 {
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return -(long)e;
-    hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_kernels,
+    hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp};
     long total = 0;
     for (auto fn : take) {
@@ -476,7 +476,7 @@ int ldpc_ctx_create(int device, const ldpc_graph *g, int max_batch, ldpc_ctx **o
                          o_ba = o_pb + al(4 * n_pb), o_pd = o_ba + al(4 * n_ba), o_gb = o_pd + al(n_pd),
                          o_er = o_gb + al(4 * n_gb), n_er = (size_t)fh.e_pad + 64, tot = o_er + al(4 * n_er);
             // element -> (row, position) of the c2v layout: the packed-message bit phase
-            // (kernels.hip k_flood_bit_packed) rebuilds a message from its row's state
+            // (flood.hip k_flood_bit_packed) rebuilds a message from its row's state
             std::vector<uint32_t> eref(n_er, 0);
             for (int i = 0; i < fh.M_pad; ++i)
                 for (int k = 0; k < fh.rdeg[i]; ++k)
@@ -670,161 +670,73 @@ static int nms_setup(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, ldpc::DecodeArgs 
     return LDPC_OK;
 }
 
-// LDPC_OPT_KERNEL: the generic kernel a test forces (kernels.hip choose_kernel).
-static const char *forced_kernel(const ldpc_ctx *c)
+// The launch plan of a decode (kernels.h): which kernel, its shape, grid and scratch. The
+// families' planners are asked in the order of preference (each says whether its kernel
+// decodes the input); LDPC_OPT_KERNEL (tests) forces one of the generic kernels.
+static ldpc::LaunchPlan build_plan(const ldpc_ctx *c, const ldpc::DecodeArgs &a, bool f64, int schedule)
 {
-    static const char *const names[] = {nullptr, "lds", "flood", "global"};
-    return names[c->opts.v[LDPC_OPT_KERNEL]];
-}
-
-static ldpc::KernelChoice select_kernel(const ldpc_ctx *c, bool f64, int schedule, int variant)
-{
+    enum { AUTO = 0, LDS = 1, FLOOD = 2, GLOBAL = 3 };   // values of LDPC_OPT_KERNEL
     const ldpc::OptScope os(c->opts);
-    if (variant == LDPC_BP) return ldpc::bp_choose(c->dg, f64, c->g->E);
-    if (schedule == LDPC_LAYERED) return ldpc::choose_layered(c->dg, f64, c->fs, c->ls, forced_kernel(c));
-    return ldpc::choose_kernel(c->dg, f64, c->has_rs ? &c->rs : nullptr, forced_kernel(c), c->has_fs ? &c->fs : nullptr);
-}
-
-static bool is_layered(const ldpc::KernelChoice &kc) { return kc.name[0] == 'l' && kc.name[1] == 'a'; }
-
-// The ping-pong kernel's schedule: the degree-aware row slots (graph.h
-// pp_row_slots) when the code admits them, else the row kernel's.
-static const ldpc::RowSched &pp_sched(const ldpc_ctx *c)
-{
-    if (c->opts.v[LDPC_OPT_PP_SLOTS] == 1) return c->rs;   // tests / A/B: the row kernel's slots
-    return c->has_rs_pp ? c->rs_pp : c->rs;
-}
-
-// Row graphs on the fast path: a kernel holding only the fast check node plus the
-// exact re-decode (k_redo) of the codewords whose premise failed.
-//   fp64: the ping-pong kernel (rows_pp.hip: two codewords per 1024-thread block,
-//         check and bit waves overlapped) when the schedule fits it, else the
-//         one-codeword-per-block k_rows_fast (LDPC_OPT_ROWS64 = 1 forces the latter);
-//   fp32: pairs as float2 -- MS and NMS with the verified reciprocal (a after
-//         nms_setup) -- on the ping-pong kernel (7.4 vs 8.8 ms per bench launch for
-//         the row kernel), on the pair instance of k_rows_fast with
-//         LDPC_OPT_ROWS32 = 1, on the row kernel (kernels.hip k_decode_rows, fast and
-//         exact loops in one) with LDPC_OPT_ROWS32 = 2 and for everything else (OMS,
-//         codes the ping-pong schedule does not fit).
-// LDPC_OPT_ROWS64 = 2 keeps the row kernel for fp64 too.
-enum class FastKind { none, pp, fast };
-static FastKind fast_kind(const ldpc_ctx *c, const ldpc::KernelChoice &kc, bool f64, const ldpc::DecodeArgs &a)
-{
-    const int r64 = c->opts.v[LDPC_OPT_ROWS64], r32 = c->opts.v[LDPC_OPT_ROWS32];
-    if (f64 && r64 == 2) return FastKind::none;
-    if (kc.name[0] != 'r' || !c->has_rs || ldpc::redo_lds_bytes(c->dg, f64) > 160 * 1024) return FastKind::none;
-    const bool pp_ok = ldpc::rows_pp_supported(c->dg, pp_sched(c));
-    if (f64) {
-        if (pp_ok && r64 == 0) return FastKind::pp;
-        return ldpc::rows_fast_supported(c->rs, true) ? FastKind::fast : FastKind::none;
-    }
-    if (!ldpc::rows_fast_f32_ok(a)) return FastKind::none;
-    if (r32 == 1) return ldpc::rows_fast_supported(c->rs, false) ? FastKind::fast : FastKind::none;
-    if (r32 == 2) return FastKind::none;
-    return pp_ok ? FastKind::pp : FastKind::none;
-}
-static bool use_rows_fast(const ldpc_ctx *c, const ldpc::KernelChoice &kc, bool f64, const ldpc::DecodeArgs &a)
-{
-    return fast_kind(c, kc, f64, a) != FastKind::none;
-}
-static bool use_rows_pp(const ldpc_ctx *c, const ldpc::KernelChoice &kc, bool f64, const ldpc::DecodeArgs &a)
-{
-    return fast_kind(c, kc, f64, a) == FastKind::pp;
-}
-
-// Flooding of codes beyond LDS: one launch per phase over an Infinity-Cache-
-// resident set (default; 1.5x the persistent kernel on DVB-S2) or the
-// persistent workgroup-per-codeword kernel (LDPC_OPT_FLOOD_MODE = 1).
-static bool use_flood_phase(const ldpc_ctx *c) { return c->opts.v[LDPC_OPT_FLOOD_MODE] != 1; }
-
-// Resident-state budget of the global layered kernel (bytes its resident codewords touch):
-// within MI355X's 256 MiB Infinity Cache with room for the schedule and the rest of the
-// working set (measured knee: 208.5 MiB fine, 216 MiB 1.2x slower; api.cpp run_kernel).
-static constexpr size_t kLayeredResidentBudget = (size_t)208 << 20;
-
-static int run_kernel(ldpc_ctx *c, const ldpc::DecodeArgs &a, bool f64, int schedule)
-{
-    const ldpc::OptScope os(c->opts);
-    const ldpc::KernelChoice kc = select_kernel(c, f64, schedule, a.variant);
-    const bool layered = is_layered(kc);
+    const ldpc::PlanInput in{c->dg, c->g->E, c->has_rs ? &c->rs : nullptr, c->has_rs_pp ? &c->rs_pp : nullptr,
+                             c->has_fs ? &c->fs : nullptr, c->has_ls ? &c->ls : nullptr, c->num_cus, a, f64};
+    const int force = c->opts.v[LDPC_OPT_KERNEL];
+    ldpc::LaunchPlan p;
     if (a.variant == ldpc::VARIANT_BP) {
-        int gblocks = 0;
-        if (kc.scratch_per_block) {
-            gblocks = std::min(a.batch, 4 * c->num_cus);
-            HIP_TRY(c->gscratch.ensure(kc.scratch_per_block * (size_t)gblocks + 65536));   // + the phase kernels' counters
-        }
-        HIP_TRY(hipEventRecord(c->ev0, c->stream));
-        HIP_TRY(ldpc::bp_launch(c->dg, a, f64, kc, c->gscratch.p, gblocks, c->g->E, c->num_cus, c->stream));
-        HIP_TRY(hipEventRecord(c->ev1, c->stream));
-        c->timed = true;
-        LDPC_CHECK_AFTER_LAUNCH(c->stream);
-        return LDPC_OK;
+        ldpc::plan_bp(in, p);
+    } else if (schedule == LDPC_LAYERED) {
+        ldpc::plan_layered(in, p);   // check_cfg: the context has the layered schedule
+    } else {
+        const bool planned = (force == FLOOD && ldpc::plan_flood(in, p)) || (force == AUTO && ldpc::plan_rows(in, p)) ||
+                             ((force == AUTO || force == LDS) && ldpc::plan_lds(in, p)) ||
+                             (force != GLOBAL && ldpc::plan_flood(in, p));
+        if (!planned) ldpc::plan_global(in, p);
     }
-    int gblocks = layered ? c->num_cus : 0;
-    if (kc.scratch_per_block) {
-        int per_cu = layered ? ldpc::layered_blocks_per_cu(f64, kc) : ldpc::blocks_per_cu(c->dg, f64, kc);
-        // Global layered kernel: at most one codeword per CU, and no more resident
-        // codewords than the Infinity Cache holds (kLayeredResidentBudget: DVB-S2 fp64,
-        // 1.01 MB touched per codeword, runs 6.4 ms per codeword round at 184-216
-        // resident codewords and 7.6 / 8.7 / 9.3 ms at 224 / 240 / 256 -- the state
-        // spills to HBM; 2 per CU measured 1.5x slower); LDPC_OPT_LAYERED_BPC
-        // overrides both (experiments).
-        if (layered) {
-            const int want = c->opts.v[LDPC_OPT_LAYERED_BPC] > 0 ? c->opts.v[LDPC_OPT_LAYERED_BPC] : 1;
-            per_cu = std::min(per_cu, want);
-        } else if (const int cap = c->opts.v[LDPC_OPT_FLOOD_BPC]) {   // global flooding kernel (experiments)
-            per_cu = std::min(per_cu, cap);
-        }
-        if (per_cu <= 0) per_cu = 1;
-        gblocks = per_cu * c->num_cus;
-        if (layered && c->opts.v[LDPC_OPT_LAYERED_BPC] <= 0) {
-            const size_t fp = ldpc::layered_resident_bytes(c->fs, c->ls, f64);
-            gblocks = (int)std::min<size_t>((size_t)gblocks, std::max<size_t>(1, kLayeredResidentBudget / fp));
-        }
-        if (gblocks > a.batch) gblocks = a.batch;
-        if (layered) {   // the same number of codeword rounds on fewer resident codewords
-            const int rounds = (a.batch + gblocks - 1) / gblocks;
-            gblocks = (a.batch + rounds - 1) / rounds;
-        }
-        HIP_TRY(c->gscratch.ensure(kc.scratch_per_block * (size_t)gblocks + 65536));   // + the phase kernels' counters
-    }
+    return p;
+}
+
+static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
+{
+    using ldpc::Kernel;
+    const ldpc::OptScope os(c->opts);
+    const ldpc::LaunchPlan p = build_plan(c, a, f64, schedule);
+    if (p.scratch_bytes) HIP_TRY(c->gscratch.ensure(p.scratch_bytes));
+    if (p.redo) HIP_TRY(c->redo.ensure(sizeof(unsigned) * ((size_t)c->max_batch + 1)));
 #ifdef LDPC_STAMPS
     // diagnostic builds: per-block phase cycle sums appended to $LDPC_STAMPS
     static DevBuf stamp_buf;
-    ldpc::DecodeArgs as = a;
     const char *stamp_path = std::getenv("LDPC_STAMPS");
     if (stamp_path) {
         HIP_TRY(stamp_buf.ensure(8192 * 4 * sizeof(unsigned long long)));
         HIP_TRY(hipMemsetAsync(stamp_buf.p, 0, stamp_buf.n, c->stream));
-        as.stamps = (unsigned long long *)stamp_buf.p;
+        a.stamps = (unsigned long long *)stamp_buf.p;
     }
-#define a as
 #endif
-    // fp64 row graphs: the fast-path kernel plus the exact re-decode of any
-    // codeword whose premise failed (LDPC_ROWS=old keeps the old row kernel).
-    const bool fast = use_rows_fast(c, kc, f64, a);
-    if (fast) HIP_TRY(c->redo.ensure(sizeof(unsigned) * ((size_t)c->max_batch + 1)));
     HIP_TRY(hipEventRecord(c->ev0, c->stream));
-    c->last_fast = fast;
-    if (fast) {
-        HIP_TRY(hipMemsetAsync(c->redo.p, 0, sizeof(unsigned), c->stream));
-        if (use_rows_pp(c, kc, f64, a))
-            HIP_TRY(ldpc::launch_rows_pp(c->dg, pp_sched(c), a, f64, (unsigned *)c->redo.p, c->stream, c->num_cus));
-        else
-            HIP_TRY(ldpc::launch_rows_fast(c->dg, c->rs, a, f64, kc.lds_bytes, (unsigned *)c->redo.p, c->stream,
-                                           c->num_cus));
-        HIP_TRY(ldpc::launch_redo(c->dg, a, f64, (const unsigned *)c->redo.p, c->stream, c->num_cus));
-    } else if (layered) {
-        HIP_TRY(ldpc::launch_layered(c->dg, a, f64, kc, c->fs, c->ls, c->gscratch.p, gblocks, c->stream));
-    } else if (kc.name[0] == 'f' && use_flood_phase(c))
-        HIP_TRY(ldpc::launch_flood_phase(c->dg, c->fs, a, f64, kc, c->gscratch.p, c->gscratch.n, c->stream, &c->aux));
-    else
-        HIP_TRY(ldpc::launch_decode(c->dg, a, f64, kc, c->gscratch.p, gblocks, c->stream,
-                                    c->has_rs ? &c->rs : nullptr, c->num_cus, c->has_fs ? &c->fs : nullptr));
+    c->last_fast = p.redo;
+    if (p.redo) HIP_TRY(hipMemsetAsync(c->redo.p, 0, sizeof(unsigned), c->stream));
+    switch (p.kernel) {
+    case Kernel::rows: HIP_TRY(ldpc::launch_rows(p, c->dg, a, c->stream)); break;
+    case Kernel::rows_fast: HIP_TRY(ldpc::launch_rows_fast(p, c->dg, a, (unsigned *)c->redo.p, c->stream)); break;
+    case Kernel::rows_pp: HIP_TRY(ldpc::launch_rows_pp(p, c->dg, a, (unsigned *)c->redo.p, c->stream)); break;
+    case Kernel::lds:
+    case Kernel::global: HIP_TRY(ldpc::launch_generic(p, c->dg, a, c->gscratch.p, c->stream)); break;
+    case Kernel::flood_persistent:
+    case Kernel::flood_phase:
+        HIP_TRY(ldpc::launch_flood(p, c->dg, c->fs, a, f64, c->gscratch.p, c->stream, &c->aux));
+        break;
+    case Kernel::layered_lds:
+    case Kernel::layered_global:
+        HIP_TRY(ldpc::launch_layered(p, c->dg, c->fs, c->ls, a, c->gscratch.p, c->stream));
+        break;
+    case Kernel::bp_rows:
+    case Kernel::bp_lds:
+    case Kernel::bp_global: HIP_TRY(ldpc::launch_bp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->stream)); break;
+    }
+    // the exact re-decode of any codeword whose fast-path premise failed
+    if (p.redo) HIP_TRY(ldpc::launch_redo(c->dg, a, f64, (const unsigned *)c->redo.p, c->stream, c->num_cus));
     HIP_TRY(hipEventRecord(c->ev1, c->stream));
     c->timed = true;
 #ifdef LDPC_STAMPS
-#undef a
     if (stamp_path) {
         std::vector<unsigned long long> h(8192 * 4);
         HIP_TRY(hipMemcpyAsync(h.data(), stamp_buf.p, stamp_buf.n, hipMemcpyDeviceToHost, c->stream));
@@ -838,7 +750,6 @@ static int run_kernel(ldpc_ctx *c, const ldpc::DecodeArgs &a, bool f64, int sche
     LDPC_CHECK_AFTER_LAUNCH(c->stream);
     return LDPC_OK;
 }
-
 
 static int read_counts(ldpc_ctx *c, ldpc_counts *out, int reset)
 {
@@ -866,6 +777,45 @@ static void accumulate(ldpc_counts *acc, const ldpc_counts &d)
     acc->iters += d.iters;
     acc->syndrome_fail += d.syndrome_fail;
 }
+
+static int counts_delta(ldpc_ctx *c, const ldpc_counts &before, ldpc_counts *acc)
+{
+    ldpc_counts after;
+    int rc = read_counts(c, &after, 0);
+    if (rc) return rc;
+    if (acc) {
+        ldpc_counts d;
+        d.bit_err = after.bit_err - before.bit_err;
+        d.frame_err = after.frame_err - before.frame_err;
+        d.uncoded_bit_err = after.uncoded_bit_err - before.uncoded_bit_err;
+        d.frames = after.frames - before.frames;
+        d.iters = after.iters - before.iters;
+        d.syndrome_fail = after.syndrome_fail - before.syndrome_fail;
+        accumulate(acc, d);
+    }
+    return LDPC_OK;
+}
+
+// An output the caller may hold on the host or on the device: the kernel writes dev (the
+// caller's own pointer, or the staging buffer when that is host memory; null: not wanted),
+// and fetch() copies a staged output back once the launch is queued.
+struct OutStage {
+    void *user = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    hipError_t bind(void *out, DevBuf &stage, size_t n)
+    {
+        user = dev = out;
+        bytes = n;
+        if (!out || is_device_ptr(out)) return hipSuccess;
+        const hipError_t e = stage.ensure(n);
+        dev = stage.p;
+        return e;
+    }
+    hipError_t fetch(hipStream_t s) const
+    {
+        return dev == user ? hipSuccess : hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s);
+    }
+};
 
 // ----------------------------------------------------------------- decode
 int ldpc_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_decoder_cfg *cfg, const int8_t *cw,
@@ -907,43 +857,19 @@ int ldpc_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_decoder_
             a.c = (const int8_t *)c->c_stage.p;
         }
     }
-    const bool d_host = d_out && !is_device_ptr(d_out);
-    const bool w_host = frame_weights && !is_device_ptr(frame_weights);
-    if (d_host) {
-        HIP_TRY(c->d_stage.ensure(nbytes));
-        a.d_out = (int8_t *)c->d_stage.p;
-    } else {
-        a.d_out = d_out;
-    }
-    if (w_host) {
-        HIP_TRY(c->fw_stage.ensure(sizeof(ldpc_frame_result) * (size_t)batch));
-        a.frame_res = (int4 *)c->fw_stage.p;
-    } else {
-        a.frame_res = (int4 *)frame_weights;
-    }
+    OutStage d, w;
+    HIP_TRY(d.bind(d_out, c->d_stage, nbytes));
+    HIP_TRY(w.bind(frame_weights, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    a.d_out = (int8_t *)d.dev;
+    a.frame_res = (int4 *)w.dev;
     ldpc_counts before;
     rc = read_counts(c, &before, 0);
     if (rc) return rc;
     rc = run_kernel(c, a, f64, cfg->schedule);
     if (rc) return rc;
-    if (d_host) HIP_TRY(hipMemcpyAsync(d_out, c->d_stage.p, nbytes, hipMemcpyDeviceToHost, c->stream));
-    if (w_host)
-        HIP_TRY(hipMemcpyAsync(frame_weights, c->fw_stage.p, sizeof(ldpc_frame_result) * (size_t)batch,
-                               hipMemcpyDeviceToHost, c->stream));
-    ldpc_counts after;
-    rc = read_counts(c, &after, 0);
-    if (rc) return rc;
-    if (counts) {
-        ldpc_counts d;
-        d.bit_err = after.bit_err - before.bit_err;
-        d.frame_err = after.frame_err - before.frame_err;
-        d.uncoded_bit_err = after.uncoded_bit_err - before.uncoded_bit_err;
-        d.frames = after.frames - before.frames;
-        d.iters = after.iters - before.iters;
-        d.syndrome_fail = after.syndrome_fail - before.syndrome_fail;
-        accumulate(counts, d);
-    }
-    return LDPC_OK;
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    return counts_delta(c, before, counts);
 }
 
 // ----------------------------------------------------------------- Monte-Carlo
@@ -1039,45 +965,17 @@ static int sim_sync_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decod
     ldpc_counts before;
     rc = read_counts(c, &before, 0);
     if (rc) return rc;
-    const bool w_host = frames && !is_device_ptr(frames);
-    const bool y_host = y_out && !is_device_ptr(y_out);
-    const bool d_host = d_out && !is_device_ptr(d_out);
-    ldpc_frame_result *fw_dev = frames;
-    void *y_dev = y_out;
-    int8_t *d_dev = d_out;
-    if (w_host) {
-        HIP_TRY(c->fw_stage.ensure(sizeof(ldpc_frame_result) * (size_t)batch));
-        fw_dev = (ldpc_frame_result *)c->fw_stage.p;
-    }
-    if (y_host) {
-        HIP_TRY(c->y_stage.ensure(ybytes));
-        y_dev = c->y_stage.p;
-    }
-    if (d_host) {
-        HIP_TRY(c->d_stage.ensure(nb));
-        d_dev = (int8_t *)c->d_stage.p;
-    }
-    rc = sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, fw_dev, y_dev, d_dev);
+    OutStage w, y, d;
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    HIP_TRY(y.bind(y_out, c->y_stage, ybytes));
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    rc = sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev, y.dev,
+                         (int8_t *)d.dev);
     if (rc) return rc;
-    if (w_host)
-        HIP_TRY(hipMemcpyAsync(frames, fw_dev, sizeof(ldpc_frame_result) * (size_t)batch, hipMemcpyDeviceToHost,
-                               c->stream));
-    if (y_host) HIP_TRY(hipMemcpyAsync(y_out, y_dev, ybytes, hipMemcpyDeviceToHost, c->stream));
-    if (d_host) HIP_TRY(hipMemcpyAsync(d_out, d_dev, nb, hipMemcpyDeviceToHost, c->stream));
-    ldpc_counts after;
-    rc = read_counts(c, &after, 0);
-    if (rc) return rc;
-    if (accum) {
-        ldpc_counts d;
-        d.bit_err = after.bit_err - before.bit_err;
-        d.frame_err = after.frame_err - before.frame_err;
-        d.uncoded_bit_err = after.uncoded_bit_err - before.uncoded_bit_err;
-        d.frames = after.frames - before.frames;
-        d.iters = after.iters - before.iters;
-        d.syndrome_fail = after.syndrome_fail - before.syndrome_fail;
-        accumulate(accum, d);
-    }
-    return LDPC_OK;
+    HIP_TRY(w.fetch(c->stream));
+    HIP_TRY(y.fetch(c->stream));
+    HIP_TRY(d.fetch(c->stream));
+    return counts_delta(c, before, accum);
 }
 
 int ldpc_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
@@ -1103,38 +1001,43 @@ int ldpc_ctx_last_kernel_ms(ldpc_ctx *c, float *ms)
     return LDPC_OK;
 }
 
-int ldpc_ctx_row_sched_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *info)
+// The plan of cfg as the info calls report it (a one-codeword batch, no sample source).
+static int info_plan(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, ldpc::LaunchPlan &p)
 {
-    if (!c || !cfg || !info) return set_err(LDPC_ERR_INVALID, "null argument");
-    const bool f64 = cfg->precision == LDPC_F64;
+    if (!c || !cfg) return set_err(LDPC_ERR_INVALID, "null argument");
+    HIP_TRY(hipSetDevice(c->device));
     int rc = check_cfg(c, cfg);
     if (rc) return rc;
-    const ldpc::KernelChoice kc = select_kernel(c, f64, cfg->schedule, cfg->variant);
-    if (cfg->variant == LDPC_BP || !c->has_rs || std::strcmp(kc.name, "rows") != 0)
-        return set_err(LDPC_ERR_UNSUPPORTED, "the row kernel does not decode this cfg (kernel %s)", kc.name);
-    info[0] = c->rs.threads;
-    info[1] = c->rs.rpt;
-    info[2] = c->rs.cpt;
-    info[3] = c->rs.dc;
-    info[4] = c->rs.e_pad;
-    info[5] = kc.cw_per_block;
-    info[6] = kc.lds_bytes;
-    info[7] = ldpc::blocks_per_cu(c->dg, f64, kc);
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, 1);
     rc = nms_setup(c, cfg, a);   // fp32 NMS: whether the verified reciprocal (and so the fast kernels) applies
     if (rc) return rc;
-    info[8] = 0;
-    info[9] = c->rs.threads * c->rs.rpt * c->rs.dc;   // check edge slots issued per codeword-iteration
-    if (use_rows_pp(c, kc, f64, a)) {   // one 1024-thread block per CU
-        const ldpc::RowSched &rs = pp_sched(c);
-        info[6] = ldpc::rows_pp_lds_bytes(c->dg, rs);
-        info[7] = 1;
-        info[8] = rs.dc_low;
-        // degree-aware slots (rows_pp.hip k_rows_pp SPLIT): every row-0 slot and the row-1 slots of
-        // threads >= threads/2 run a dc_low-edge check node, the other row-1 slots a dc-edge one
-        if (rs.dc_low) info[9] = (rs.threads + rs.threads / 2) * rs.dc_low + (rs.threads / 2) * rs.dc;
-    }
+    p = build_plan(c, a, cfg->precision == LDPC_F64, cfg->schedule);
+    return LDPC_OK;
+}
+
+int ldpc_ctx_row_sched_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *info)
+{
+    if (!info) return set_err(LDPC_ERR_INVALID, "null argument");
+    ldpc::LaunchPlan p;
+    const int rc = info_plan(c, cfg, p);
+    if (rc) return rc;
+    if (!p.rs) return set_err(LDPC_ERR_UNSUPPORTED, "the row kernel does not decode this cfg (kernel %s)", p.name);
+    const ldpc::RowSched &rs = *p.rs;
+    info[0] = rs.threads;
+    info[1] = rs.rpt;
+    info[2] = rs.cpt;
+    info[3] = rs.dc;
+    info[4] = rs.e_pad;
+    info[5] = p.cw_per_block;
+    info[6] = p.lds_bytes;
+    info[7] = p.blocks_per_cu;
+    info[8] = rs.dc_low;
+    // check edge slots issued per codeword-iteration; with degree-aware slots (rows_pp.hip k_rows_pp
+    // SPLIT) every row-0 slot and the row-1 slots of threads >= threads/2 run a dc_low-edge check
+    // node, the other row-1 slots a dc-edge one
+    info[9] = rs.dc_low ? (rs.threads + rs.threads / 2) * rs.dc_low + (rs.threads / 2) * rs.dc
+                        : rs.threads * rs.rpt * rs.dc;
     return LDPC_OK;
 }
 
@@ -1154,27 +1057,12 @@ int ldpc_ctx_redo_count(ldpc_ctx *c, int64_t *n)
 int ldpc_ctx_kernel_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, char *name, int name_len, int *lds_bytes,
                          int *bpc)
 {
-    if (!c || !cfg) return set_err(LDPC_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    const bool f64 = cfg->precision == LDPC_F64;
-    int rc = check_cfg(c, cfg);
+    ldpc::LaunchPlan p;
+    const int rc = info_plan(c, cfg, p);
     if (rc) return rc;
-    const ldpc::KernelChoice kc = select_kernel(c, f64, cfg->schedule, cfg->variant);
-    ldpc::DecodeArgs a;
-    fill_common(a, c, cfg, 1);
-    rc = nms_setup(c, cfg, a);   // fp32 NMS: whether the verified reciprocal (and so the fast kernel) applies
-    if (rc) return rc;
-    if (name && name_len > 0)
-        std::snprintf(name, (size_t)name_len, "%s",
-                      cfg->variant != LDPC_BP && use_rows_fast(c, kc, f64, a) ? (use_rows_pp(c, kc, f64, a) ? "rows_pp" : "rows_fast")
-                                                                                : kc.name);
-    if (lds_bytes) *lds_bytes = kc.lds_bytes;
-    if (bpc) *bpc = cfg->variant == LDPC_BP ? 0 : is_layered(kc) ? (kc.lds_bytes ? 0 : ldpc::layered_blocks_per_cu(f64, kc))
-                                   : ldpc::blocks_per_cu(c->dg, f64, kc);
-    if (cfg->variant != LDPC_BP && use_rows_pp(c, kc, f64, a)) {
-        if (lds_bytes) *lds_bytes = ldpc::rows_pp_lds_bytes(c->dg, pp_sched(c));
-        if (bpc) *bpc = 1;
-    }
+    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", p.name);
+    if (lds_bytes) *lds_bytes = p.lds_bytes;
+    if (bpc) *bpc = p.blocks_per_cu;
     return LDPC_OK;
 }
 
@@ -1237,24 +1125,6 @@ static int gdbf_run(ldpc_ctx *c, const ldpc::GdbfArgs &a, bool f64)
     return LDPC_OK;
 }
 
-static int counts_delta(ldpc_ctx *c, const ldpc_counts &before, ldpc_counts *acc)
-{
-    ldpc_counts after;
-    int rc = read_counts(c, &after, 0);
-    if (rc) return rc;
-    if (acc) {
-        ldpc_counts d;
-        d.bit_err = after.bit_err - before.bit_err;
-        d.frame_err = after.frame_err - before.frame_err;
-        d.uncoded_bit_err = after.uncoded_bit_err - before.uncoded_bit_err;
-        d.frames = after.frames - before.frames;
-        d.iters = after.iters - before.iters;
-        d.syndrome_fail = after.syndrome_fail - before.syndrome_fail;
-        accumulate(acc, d);
-    }
-    return LDPC_OK;
-}
-
 int ldpc_gdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_gdbf_cfg *cfg,
                            const int8_t *cw, int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
 {
@@ -1299,29 +1169,18 @@ int ldpc_gdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int bat
             a.c = (const int8_t *)c->c_stage.p;
         }
     }
-    const bool d_host = d_out && !is_device_ptr(d_out);
-    const bool w_host = frames && !is_device_ptr(frames);
-    if (d_host) {
-        HIP_TRY(c->d_stage.ensure(nb));
-        a.d_out = (int8_t *)c->d_stage.p;
-    } else {
-        a.d_out = d_out;
-    }
-    if (w_host) {
-        HIP_TRY(c->fw_stage.ensure(sizeof(ldpc_frame_result) * (size_t)batch));
-        a.frame_res = (int4 *)c->fw_stage.p;
-    } else {
-        a.frame_res = (int4 *)frames;
-    }
+    OutStage d, w;
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    a.d_out = (int8_t *)d.dev;
+    a.frame_res = (int4 *)w.dev;
     ldpc_counts before;
     rc = read_counts(c, &before, 0);
     if (rc) return rc;
     rc = gdbf_run(c, a, f64);
     if (rc) return rc;
-    if (d_host) HIP_TRY(hipMemcpyAsync(d_out, c->d_stage.p, nb, hipMemcpyDeviceToHost, c->stream));
-    if (w_host)
-        HIP_TRY(hipMemcpyAsync(frames, c->fw_stage.p, sizeof(ldpc_frame_result) * (size_t)batch,
-                               hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
     return counts_delta(c, before, counts);
 }
 
@@ -1369,17 +1228,11 @@ int ldpc_gdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_c
     ldpc_counts before;
     int rc = read_counts(c, &before, 0);
     if (rc) return rc;
-    const bool w_host = frames && !is_device_ptr(frames);
-    ldpc_frame_result *fw_dev = frames;
-    if (w_host) {
-        HIP_TRY(c->fw_stage.ensure(sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
-        fw_dev = (ldpc_frame_result *)c->fw_stage.p;
-    }
-    rc = gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, fw_dev);
+    OutStage w;   // batch is checked by gdbf_sim_impl
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
+    rc = gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev);
     if (rc) return rc;
-    if (w_host)
-        HIP_TRY(hipMemcpyAsync(frames, fw_dev, sizeof(ldpc_frame_result) * (size_t)batch, hipMemcpyDeviceToHost,
-                               c->stream));
+    HIP_TRY(w.fetch(c->stream));
     return counts_delta(c, before, accum);
 }
 

@@ -18,6 +18,7 @@
 #include "device_common.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -477,94 +478,65 @@ static bool bp_rows_forced_off() { return opt(LDPC_OPT_BP_KERNEL) == 1; }
 
 constexpr size_t kBpMaxLds = 160 * 1024;
 
-KernelChoice bp_choose(const DevGraph &g, bool f64, int E)
-{
-    KernelChoice kc;
-    if (bp_rows_fits(g, E, f64) && !bp_rows_forced_off()) {
-        kc.name = "bp_rows";
-        kc.threads = g.N <= 4 * 512 && g.M <= 2 * 512 ? 512 : 1024;
-        kc.cw_per_block = 1;
-        kc.lds_bytes = bp_rows_layout(g.N, E, f64 ? 8 : 4).total;
-        kc.scratch_per_block = 0;
-        return kc;
-    }
-    kc.threads = 512;   // measured (N=1944 fp32): 256 -> 1.06, 512 -> 1.50, 1024 -> 0.92 Gbit/s
-    kc.cw_per_block = 1;
-    const size_t st = bp_state_bytes(g, f64 ? 8 : 4);
-    if (st <= kBpMaxLds) {
-        kc.name = "bp_lds";
-        kc.lds_bytes = (int)st;
-        kc.scratch_per_block = 0;
-    } else {
-        kc.name = "bp_global";
-        kc.lds_bytes = 0;
-        kc.scratch_per_block = st;
-    }
-    return kc;
-}
-
-template <typename F, int SRC, int NT>
-static hipError_t bp_rows_launch(const DevGraph &g, const DecodeArgs &a, const KernelChoice &kc, int E, int num_cus,
-                                 hipStream_t s)
-{
-    const BpRowsLayout L = bp_rows_layout(g.N, E, (int)sizeof(F));
-    auto fn = k_bp_rows<F, SRC, NT>;
-    if (L.total > 64 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, L.total);
-        if (e != hipSuccess) return e;
-    }
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, NT, L.total) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    int grid = per_cu * (num_cus > 0 ? num_cus : 1);
-    if (grid > a.batch) grid = a.batch;
-    (void)kc;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(NT), L.total, s, a, g, L.msg_off, E);
-    return hipGetLastError();
-}
-
-template <typename F, int SRC, int DCB>
-static hipError_t bp_launch_d(const DevGraph &g, const DecodeArgs &a, const KernelChoice &kc, void *gs, int gblocks,
-                              hipStream_t s)
-{
-    if (kc.lds_bytes > 0) {
-        auto fn = k_bp_lds<F, SRC, DCB>;
-        if (kc.lds_bytes > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               kc.lds_bytes);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(fn, dim3(a.batch), dim3(kc.threads), kc.lds_bytes, s, a, g);
-    } else {
-        const int grid = gblocks < a.batch ? gblocks : a.batch;
-        if (grid <= 0 || !gs) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((k_bp_global<F, SRC, DCB>), dim3(grid), dim3(kc.threads), 0, s, a, g, (unsigned char *)gs,
-                           kc.scratch_per_block);
-    }
-    return hipGetLastError();
-}
-
 template <typename F, int SRC>
-static hipError_t bp_launch_t(const DevGraph &g, const DecodeArgs &a, const KernelChoice &kc, void *gs, int gblocks,
-                              int E, int num_cus, hipStream_t s)
+static const void *bp_fn(const DevGraph &g, Kernel k, int threads)
 {
-    if (kc.name[3] == 'r')   // "bp_rows"
-        return kc.threads == 512 ? bp_rows_launch<F, SRC, 512>(g, a, kc, E, num_cus, s)
-                                 : bp_rows_launch<F, SRC, 1024>(g, a, kc, E, num_cus, s);
-    if (g.dcs <= 8) return bp_launch_d<F, SRC, 8>(g, a, kc, gs, gblocks, s);
-    if (g.dcs <= 16) return bp_launch_d<F, SRC, 16>(g, a, kc, gs, gblocks, s);
-    return bp_launch_d<F, SRC, kBpMaxDc>(g, a, kc, gs, gblocks, s);
+    if (k == Kernel::bp_rows)
+        return threads == 512 ? (const void *)k_bp_rows<F, SRC, 512> : (const void *)k_bp_rows<F, SRC, 1024>;
+    const bool lds = k == Kernel::bp_lds;
+    if (g.dcs <= 8) return lds ? (const void *)k_bp_lds<F, SRC, 8> : (const void *)k_bp_global<F, SRC, 8>;
+    if (g.dcs <= 16) return lds ? (const void *)k_bp_lds<F, SRC, 16> : (const void *)k_bp_global<F, SRC, 16>;
+    return lds ? (const void *)k_bp_lds<F, SRC, kBpMaxDc> : (const void *)k_bp_global<F, SRC, kBpMaxDc>;
 }
 
-hipError_t bp_launch(const DevGraph &g, const DecodeArgs &a, bool f64, const KernelChoice &kc, void *gscratch,
-                     int gblocks, int E, int num_cus, hipStream_t s)
+void plan_bp(const PlanInput &in, LaunchPlan &p)
 {
-    if (a.batch <= 0) return hipSuccess;
-    if (f64)
-        return a.src == SRC_GIVEN ? bp_launch_t<double, SRC_GIVEN>(g, a, kc, gscratch, gblocks, E, num_cus, s)
-                                  : bp_launch_t<double, SRC_PHILOX>(g, a, kc, gscratch, gblocks, E, num_cus, s);
-    return a.src == SRC_GIVEN ? bp_launch_t<float, SRC_GIVEN>(g, a, kc, gscratch, gblocks, E, num_cus, s)
-                              : bp_launch_t<float, SRC_PHILOX>(g, a, kc, gscratch, gblocks, E, num_cus, s);
+    const DevGraph &g = in.g;
+    p = LaunchPlan{};
+    const size_t st = bp_state_bytes(g, in.f64 ? 8 : 4);
+    if (bp_rows_fits(g, in.E, in.f64) && !bp_rows_forced_off()) {
+        p.kernel = Kernel::bp_rows;
+        p.name = "bp_rows";
+        p.threads = g.N <= 4 * 512 && g.M <= 2 * 512 ? 512 : 1024;
+        p.lds_bytes = bp_rows_layout(g.N, in.E, in.f64 ? 8 : 4).total;
+    } else {
+        p.threads = 512;   // measured (N=1944 fp32): 256 -> 1.06, 512 -> 1.50, 1024 -> 0.92 Gbit/s
+        if (st <= kBpMaxLds) {
+            p.kernel = Kernel::bp_lds;
+            p.name = "bp_lds";
+            p.lds_bytes = (int)st;
+        } else {
+            p.kernel = Kernel::bp_global;
+            p.name = "bp_global";
+            p.scratch_per_block = st;
+        }
+    }
+    p.fn = for_f_src(in.f64, in.a.src, [&](auto f, auto s) {
+        return bp_fn<typename decltype(f)::type, decltype(s)::value>(g, p.kernel, p.threads);
+    });
+    if (p.kernel == Kernel::bp_rows) {   // persistent: what the CU holds
+        const int per_cu = std::max(1, occupancy(p.fn, p.threads, p.lds_bytes));
+        p.grid = std::min(per_cu * (in.num_cus > 0 ? in.num_cus : 1), in.a.batch);
+    } else if (p.kernel == Kernel::bp_lds) {
+        p.grid = in.a.batch;
+    } else {
+        p.grid = std::min(in.a.batch, 4 * in.num_cus);
+        p.scratch_bytes = p.scratch_per_block * (size_t)p.grid;
+    }
+}
+
+hipError_t launch_bp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, bool f64, int E, void *gscratch,
+                     hipStream_t s)
+{
+    if (p.kernel == Kernel::bp_rows) {
+        int msg_off = bp_rows_layout(g.N, E, f64 ? 8 : 4).msg_off;
+        void *args[] = {(void *)&a, (void *)&g, &msg_off, &E};
+        return launch_fn(p, args, s);
+    }
+    unsigned char *gs = (unsigned char *)gscratch;
+    size_t sb = p.scratch_per_block;
+    void *args[] = {(void *)&a, (void *)&g, &gs, &sb};   // bp_lds takes the first two
+    return launch_fn(p, args, s);
 }
 
 }  // namespace ldpc

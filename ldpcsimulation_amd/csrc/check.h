@@ -91,7 +91,8 @@ __device__ __forceinline__ uint32_t chk_idx(uint32_t i, uint32_t n, unsigned sit
 long check_collect(hipStream_t s, char *msg, size_t msg_len);
 hipError_t check_take_rows_pp(CheckRec *out);
 hipError_t check_take_rows_fast(CheckRec *out);
-hipError_t check_take_kernels(CheckRec *out);
+hipError_t check_take_flood(CheckRec *out);
+hipError_t check_take_layered(CheckRec *out);
 hipError_t check_take_gdbf(CheckRec *out);
 hipError_t check_take_nb(CheckRec *out);
 hipError_t check_take_bp(CheckRec *out);

@@ -1,5 +1,6 @@
 // device_common.h -- device helpers shared by the decoder kernels
-// (kernels.hip: min-sum; gdbf.hip: GDBF / NGDBF bit flipping).
+// (the min-sum kernel files kernels.hip, rows.hip, flood.hip, layered.hip, rows_fast.hip, rows_pp.hip;
+// gdbf.hip: GDBF / NGDBF bit flipping).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -27,7 +27,7 @@ namespace ldpc {
 constexpr int kMaxRowDegree = 58;   // sign bits that fit the packed row state
 constexpr int kRefShift = 6;
 
-// Static work schedule of the row-parallel kernel (kernels.hip, k_decode_rows):
+// Static work schedule of the row-parallel kernel (rows.hip, k_decode_rows):
 // RPT check rows per thread (thread t owns rows t, t + threads, ...) and up to
 // CPT bit-node slots per thread. Columns are sorted by degree (stable) and cut into 64-column groups
 // of near-uniform degree; edge kc (nlist order) of the group's column l lives
@@ -48,7 +48,7 @@ struct RowSchedule {
 // an error message.
 std::string build_graph(int N, int M, const int *num_nlist, const int *const *nlist,
                         const int *num_mlist, const int *const *mlist, ldpc_graph &g);
-// Static schedule of the global-memory flooding kernel (kernels.hip,
+// Static schedule of the global-memory flooding kernel (flood.hip,
 // k_decode_flood) for codes whose state does not fit on chip (DVB-S2 N=64800).
 // Quasi-cyclic structure is discovered, not assumed: every row is chained to
 // the row that holds most of its columns + 1, edge slots are aligned along the
@@ -76,7 +76,7 @@ struct FloodSchedule {
 };
 std::string build_flood_schedule(const ldpc_graph &g, FloodSchedule &s);
 
-// Layered schedule (kernels.hip, k_decode_layered_*): rows grouped into
+// Layered schedule (layered.hip, k_decode_layered_*): rows grouped into
 // layers of rows that share no bit, by first-fit colouring of whole row
 // chains of the flood schedule (each chain -- split where it would share a
 // bit with itself -- joins the lowest layer none of its bits is in yet), so a

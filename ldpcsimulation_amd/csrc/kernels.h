@@ -1,4 +1,5 @@
-// kernels.h -- internal launch interface between api.cpp and kernels.hip.
+// kernels.h -- internal launch interface between api.cpp and the min-sum kernel files
+// (kernels.hip, rows.hip, rows_fast.hip, rows_pp.hip, flood.hip, layered.hip).
 #pragma once
 #include "options.h"
 #include <hip/hip_runtime.h>
@@ -74,27 +75,78 @@ struct LayerSched {
     const int32_t *pos_of_bit = nullptr;   // [N] layered position of each bit
 };
 
-struct KernelChoice {
-    const char *name;               // "rows", "lds", "flood" or "global"
-    int lds_bytes;                  // dynamic LDS per block
-    size_t scratch_per_block;       // global kernel
-    int threads;
-    int cw_per_block;               // rows kernel: codewords decoded together per block
+// What a plan can launch: one value per kernel family member.
+enum class Kernel {
+    rows, rows_fast, rows_pp,           // row graphs (rows.hip, rows_fast.hip, rows_pp.hip)
+    lds, global,                        // one workgroup per codeword (kernels.hip)
+    flood_persistent, flood_phase,      // codes beyond LDS (flood.hip); both report "flood"
+    layered_lds, layered_global,        // layered schedule (layered.hip)
+    bp_rows, bp_lds, bp_global          // belief propagation (bp.hip)
 };
 
-// Pick the kernel for a graph / precision. rs (may be null) is the row
-// schedule when the graph admits one; force selects "lds"/"global" for tests.
-// fs (may be null): the flood schedule, used for codes whose state exceeds LDS.
-KernelChoice choose_kernel(const DevGraph &g, bool f64, const RowSched *rs, const char *force = nullptr,
-                           const FloodSched *fs = nullptr);
-// Launch the decode. gscratch must hold choice.scratch_per_block * grid bytes
-// for the global kernel (grid returned through *grid_out, may be null).
-hipError_t launch_decode(const DevGraph &g, const DecodeArgs &a, bool f64, const KernelChoice &kc,
-                         void *gscratch, int gscratch_blocks, hipStream_t s, const RowSched *rs = nullptr,
-                         int num_cus = 256, const FloodSched *fs = nullptr);
-int blocks_per_cu(const DevGraph &g, bool f64, const KernelChoice &kc);
-// Flooding of codes beyond LDS as one launch per phase over an Infinity-Cache-
-// resident set of codewords (kernels.hip k_flood_*); gscratch as for "flood".
+// Everything one decode launch of the binary context needs, decided once (api.cpp
+// build_plan composes the families' plan_*): run_kernel sizes the scratch and launches
+// from it, ldpc_ctx_kernel_info / ldpc_ctx_row_sched_info report it.
+struct LaunchPlan {
+    Kernel kernel = Kernel::global;
+    const char *name = "";          // as reported: "rows", "rows_fast", "rows_pp", "lds", "flood", "global", ...
+    const void *fn = nullptr;       // the instantiation that launches (null: flood_phase, a launch per phase)
+    int threads = 0;
+    int lds_bytes = 0;              // dynamic LDS per block that holds decoder state, as reported
+    int layered_pos = 0;            // layered_global: P, the posteriors of the global slot cached in LDS,
+    int cache_lds_bytes = 0;        //   and their dynamic LDS (P + the dummy slot, fp64 only); not reported
+    int cw_per_block = 1;           // row kernels: codewords decoded together per thread (as reported)
+    int blocks_per_cu = 0;          // as reported; sizes the grid of the kernels that work in global scratch
+    int grid = 0;                   // blocks of the launch; flood_phase: resident slots K
+    size_t scratch_per_block = 0;   // global scratch slot of one block / resident codeword
+    size_t scratch_bytes = 0;       // scratch the launch needs in all
+    const RowSched *rs = nullptr;   // the row schedule the kernel reads (the context's rs or rs_pp)
+    bool redo = false;              // fast row kernels: a redo list goes in and launch_redo follows
+};
+
+// What the planners read. Options come through opt() (the caller's OptScope).
+struct PlanInput {
+    const DevGraph &g;
+    int E;
+    const RowSched *rs, *rs_pp;     // null where the graph admits none
+    const FloodSched *fs;           // null: none
+    const LayerSched *ls;           // null: none
+    int num_cus;
+    const DecodeArgs &a;            // after nms_setup; a.batch sizes the grid
+    bool f64;
+};
+
+// The (precision, sample source) template axes every kernel has: fn(type_tag<F>{}, src_tag<SRC>{}).
+template <typename T> struct type_tag { using type = T; };
+template <int V> struct src_tag { static constexpr int value = V; };
+template <class Fn>
+auto for_f_src(bool f64, int src, Fn &&fn)
+{
+    if (f64)
+        return src == SRC_GIVEN ? fn(type_tag<double>{}, src_tag<SRC_GIVEN>{}) : fn(type_tag<double>{}, src_tag<SRC_PHILOX>{});
+    return src == SRC_GIVEN ? fn(type_tag<float>{}, src_tag<SRC_GIVEN>{}) : fn(type_tag<float>{}, src_tag<SRC_PHILOX>{});
+}
+
+constexpr size_t kMaxLds = 160 * 1024;   // LDS one workgroup may use
+
+// Blocks of `fn` a CU holds at this shape (the dynamic LDS limit raised first); 0 on error.
+int occupancy(const void *fn, int threads, int lds_bytes);
+// One launch of plan.fn over plan.grid blocks with the plan's threads and dynamic LDS.
+hipError_t launch_fn(const LaunchPlan &p, void **args, hipStream_t s);
+
+// Each plan_* fills `p` and returns true when its kernel decodes the input; the order in
+// which api.cpp build_plan asks them is the preference order.
+//
+// kernels.hip: state in LDS ("lds") or in a global slot per block ("global", always possible).
+bool plan_lds(const PlanInput &in, LaunchPlan &p);
+void plan_global(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_generic(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, void *gscratch, hipStream_t s);
+// rows.hip: the row kernel, or one of the fast row kernels where they apply (rows_fast.hip,
+// rows_pp.hip: plan_rows_fast / plan_rows_pp amend the row kernel's plan).
+bool plan_rows(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_rows(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, hipStream_t s);
+// flood.hip: codes whose state exceeds LDS (row degree <= kPackedMaxDc), persistent or one
+// launch per phase over an Infinity-Cache-resident set of plan.grid codewords.
 // aux (may be null): a second stream with fork/join events; the resident set is
 // then split in two halves, one per stream, so one half's launch boundaries
 // overlap the other half's kernels.
@@ -102,20 +154,15 @@ struct AuxStream {
     hipStream_t s = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
 };
-hipError_t launch_flood_phase(const DevGraph &g, const FloodSched &fs, const DecodeArgs &a, bool f64,
-                              const KernelChoice &kc, void *gscratch, size_t gscratch_bytes, hipStream_t s,
-                              const AuxStream *aux = nullptr);
-
-// Layered schedule (k_decode_layered_*): state in LDS when it fits
-// ("layered_lds"), else in a global slot per block ("layered_global").
-// Requires the flood schedule (row order, storage order) and row degree <= kPackedMaxDc.
-KernelChoice choose_layered(const DevGraph &g, bool f64, const FloodSched &fs, const LayerSched &ls,
-                            const char *force = nullptr);
-hipError_t launch_layered(const DevGraph &g, const DecodeArgs &a, bool f64, const KernelChoice &kc,
-                          const FloodSched &fs, const LayerSched &ls, void *gscratch, int gscratch_blocks,
-                          hipStream_t s);
-int layered_blocks_per_cu(bool f64, const KernelChoice &kc);
-size_t layered_resident_bytes(const FloodSched &fs, const LayerSched &ls, bool f64);
+bool plan_flood(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_flood(const LaunchPlan &p, const DevGraph &g, const FloodSched &fs, const DecodeArgs &a, bool f64,
+                        void *gscratch, hipStream_t s, const AuxStream *aux);
+// layered.hip (k_decode_layered_*): state in LDS when it fits ("layered_lds"), else in a
+// global slot per block ("layered_global"). Requires the flood schedule (row order,
+// storage order) and row degree <= kPackedMaxDc.
+void plan_layered(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_layered(const LaunchPlan &p, const DevGraph &g, const FloodSched &fs, const LayerSched &ls,
+                          const DecodeArgs &a, void *gscratch, hipStream_t s);
 // Packed check state of the flood and layered kernels: a 5-bit argmin and one
 // sign bit per edge in a 32-bit meta word.
 constexpr int kPackedMaxDc = 26;
@@ -128,15 +175,15 @@ hipError_t verify_div_by_reciprocal(float alpha, float rcp, unsigned long long *
 
 // Fast-path row kernel (rows_fast.hip): fp64 (one codeword per block) and fp32
 // (a pair, dc <= 8), same LDS layout and schedule as the "rows" kernel
-// (lds_bytes of its KernelChoice), check node compiled per variant; codeword
+// (lds_bytes of its plan), check node compiled per variant; codeword
 // groups whose premise fails are appended to redo (redo[0] = count, must be 0
 // at launch; redo[1..] batch indices, capacity batch), and launch_redo
 // (kernels.hip) decodes them on the exact path. fp32 takes it only for MS and
 // for NMS with the verified reciprocal (rows_fast_f32_ok, after nms_setup).
-bool rows_fast_supported(const RowSched &rs, bool f64);
+// plan_rows_fast: p is the row kernel's plan; true and amended when the fast kernel decodes it.
+bool plan_rows_fast(const PlanInput &in, LaunchPlan &p);
 bool rows_fast_f32_ok(const DecodeArgs &a);
-hipError_t launch_rows_fast(const DevGraph &g, const RowSched &rs, const DecodeArgs &a, bool f64, int lds_bytes,
-                            unsigned *redo, hipStream_t s, int num_cus);
+hipError_t launch_rows_fast(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *redo, hipStream_t s);
 // alpha for which the fast fp64 NMS division x*r + one fma correction is exact
 bool markstein_exact_alpha(double alpha);
 size_t redo_lds_bytes(const DevGraph &g, bool f64);
@@ -147,11 +194,9 @@ hipError_t launch_redo(const DevGraph &g, const DecodeArgs &a, bool f64, const u
 // fp64 codeword or an fp32 pair (float2) each -- check waves and bit waves
 // overlapped (schedule: 512 threads, 2 rows and 4 bit slots each, dc 8, the
 // degree-aware row slots when rs.dc_low == 7); redo as above (fp32: MS and NMS
-// with the verified reciprocal, rows_fast_f32_ok).
-bool rows_pp_supported(const DevGraph &g, const RowSched &rs);
-int rows_pp_lds_bytes(const DevGraph &g, const RowSched &rs);
-hipError_t launch_rows_pp(const DevGraph &g, const RowSched &rs, const DecodeArgs &a, bool f64, unsigned *redo,
-                          hipStream_t s, int num_cus);
+// with the verified reciprocal, rows_fast_f32_ok). plan_rows_pp: as plan_rows_fast.
+bool plan_rows_pp(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_rows_pp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *redo, hipStream_t s);
 
 // Row-kernel template bounds (host picks the smallest that fits).
 constexpr int kRowsMaxThreads = 1024;

@@ -1,5 +1,5 @@
 // minsum_common.h -- device helpers shared by the min-sum kernels
-// (kernels.hip: generic/flood/layered/row kernels; rows_fast.hip: the
+// (kernels.hip, rows.hip, flood.hip, layered.hip: generic/row/flood/layered kernels; rows_fast.hip: the
 // fast-path row kernel). Reference: C_implementations/src/decodeMinSum.cpp.
 #pragma once
 #include "kernels.h"
@@ -93,7 +93,7 @@ __device__ __forceinline__ float fsub32(float a, float b)
 }
 
 // s += r for every codeword of a pack. PK (fp32 pairs only): one packed v_pk_add_f32
-// -- the fp32 row kernel (kernels.hip k_decode_rows) keeps it, 8.8 vs 10.0 ms per bench
+// -- the fp32 row kernel (rows.hip k_decode_rows) keeps it, 8.8 vs 10.0 ms per bench
 // launch for two plain adds there -- else two v_add_f32 (the ping-pong and rows_fast
 // kernels: a packed add issues slower than the two plain ones on gfx950). The choice
 // is a template parameter, so one inline function never means two things in two

@@ -38,6 +38,7 @@ struct NbArgs {
 };
 
 struct NbChoice {
+    bool ok = false;              // false: no kernel decodes the graph (degree, LDS schedule or 16-bit indices)
     const char *name = "";        // "ems_lds" | "ems_global"
     int lds_bytes = 0, threads = 0, dc = 0;
     size_t slot_bytes = 0;        // ems_global: message bytes per resident codeword

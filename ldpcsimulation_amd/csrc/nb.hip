@@ -766,9 +766,9 @@ NbChoice nb_choose(const NbDevGraph &g, int maxdc)
     // symbols (< N); the chunk stride Ep (maxdc * M rounded up to a power of two, up to
     // 65 536) only enters int offsets.
     if (maxdc > kNbMaxDc || aux > kNbMaxLds || (long)g.maxdc * g.M > 65535 || g.N > 65535) {
-        ch.name = "";   // unsupported: degree, LDS schedule or 16-bit indices
-        return ch;
+        return ch;   // unsupported (ok stays false)
     }
+    ch.ok = true;
     if (aux + msgb <= kNbMaxLds) {
         ch.name = "ems_lds";
         ch.lds_bytes = (int)(aux + msgb);
@@ -819,7 +819,7 @@ hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, v
                      int num_cus, hipStream_t s)
 {
     if (a.batch <= 0) return hipSuccess;
-    if (g.q != kNbQ || g.m != 4 || !ch.name[0]) return hipErrorInvalidValue;
+    if (g.q != kNbQ || g.m != 4 || !ch.ok) return hipErrorInvalidValue;
     int grid;
     if (ch.slot_bytes) {
         if (!scratch || slots <= 0) return hipErrorInvalidValue;

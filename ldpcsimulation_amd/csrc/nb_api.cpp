@@ -215,7 +215,7 @@ int ldpc_nb_ctx_create(int device, const ldpc_nb_graph *g, int max_batch, ldpc_n
     c->dg.col_h = base + o_ch;
     c->col_h_swz = base + o_chs;
     c->dg.maxdc = g->maxdc;
-    if (!ldpc::nb_choose(c->dg, g->maxdc).name[0]) {
+    if (!ldpc::nb_choose(c->dg, g->maxdc).ok) {
         ldpc_nb_ctx_destroy(c);
         return err(LDPC_ERR_UNSUPPORTED, "code too large for the EMS kernels (N=%d, E=%d)", g->N, g->E);
     }

@@ -2,7 +2,7 @@
 // ldpc_option, ldpc_ctx_set_option): tests and A/B measurements override the
 // library's kernel choice through the C ABI, never through the environment.
 //
-// The launch helpers deep in the kernel files (kernels.hip, nb.hip, bp.hip,
+// The launch helpers deep in the kernel files (kernels.hip, rows.hip, flood.hip, layered.hip, nb.hip, bp.hip,
 // gdbf.hip, rows_fast.hip) read them through opt(): each ABI entry point that
 // chooses or launches a kernel installs its context's options for the duration
 // of the call (OptScope). Outside such a call every option reads 0, the

@@ -1,7 +1,7 @@
 // rows_fast.hip -- the fast-path row kernel (throughput path of the flooding
 // min-sum decoder, src/decodeMinSum.cpp:247-263), fp64 first.
 //
-// Dataflow (same as kernels.hip's k_decode_rows): a 512-thread
+// Dataflow (same as rows.hip's k_decode_rows): a 512-thread
 // workgroup decodes C codewords at once for all T iterations with its whole
 // state in LDS -- app[N+2] posteriors and the c2v messages in bit-slot-major
 // order (a wave's bit-node reads are 64 consecutive words). Thread t owns
@@ -46,7 +46,7 @@
 // fp32 (C = 2 codewords per block, packed as float2) uses cn_fast of
 // minsum_common.h -- MS, and NMS with the device-verified reciprocal -- with
 // its own premise (every |c2v| and |yq| below 1e30). Opt-in (LDPC_ROWS32=fast):
-// bit-exact, but 10.05 ms per bench launch against 8.78 ms for kernels.hip's
+// bit-exact, but 10.05 ms per bench launch against 8.78 ms for rows.hip's
 // fp32 row kernel, which stays the fp32 default.
 #include "kernels.h"
 #include "device_common.h"
@@ -476,31 +476,13 @@ bool markstein_exact_alpha(double alpha)
     return (sig >> tz) < (1ull << 20);
 }
 
-template <typename F, int VAR, bool FDIV, int SRC, int DC, int CPT, int RPT>
-static hipError_t launch_fast_t(const DevGraph &g, const RowSched &rs, const DecodeArgs &a, int lds, unsigned *redo,
-                                hipStream_t s, int num_cus)
+// The instantiation for a schedule's shape; null: none is built.
+template <typename F, int VAR, bool FDIV, int SRC>
+static const void *fast_shape_fn(const RowSched &rs)
 {
     constexpr int C = sizeof(F) == 8 ? 1 : 2;
-    auto fn = k_rows_fast<F, SRC, C, DC, CPT, RPT, VAR, FDIV>;
-    hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    int per_cu = 0;
-    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, rs.threads, lds);
-    if (e != hipSuccess || per_cu < 1) per_cu = 1;
-    if (const int cap = opt(LDPC_OPT_FAST_BPC)) per_cu = std::min(per_cu, cap);   // experiments
-    const int ngrp = (a.batch + C - 1) / C;
-    int grid = per_cu * num_cus;
-    if (grid > ngrp) grid = ngrp;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(rs.threads), lds, s, a, g, rs, redo);
-    return hipGetLastError();
-}
-
-template <typename F, int VAR, bool FDIV, int SRC>
-static hipError_t launch_fast_shape(const DevGraph &g, const RowSched &rs, const DecodeArgs &a, int lds, unsigned *redo,
-                                    hipStream_t s, int num_cus)
-{
 #define LDPC_FAST_CASE(DCV, CPTV, RPTV) \
-    if (rs.dc == DCV && rs.cpt == CPTV && rs.rpt == RPTV) return launch_fast_t<F, VAR, FDIV, SRC, DCV, CPTV, RPTV>(g, rs, a, lds, redo, s, num_cus);
+    if (rs.dc == DCV && rs.cpt == CPTV && rs.rpt == RPTV) return (const void *)k_rows_fast<F, SRC, C, DCV, CPTV, RPTV, VAR, FDIV>;
     LDPC_FAST_CASE(8, 4, 2)
     LDPC_FAST_CASE(8, 2, 1)
     LDPC_FAST_CASE(8, 4, 1)
@@ -510,10 +492,10 @@ static hipError_t launch_fast_shape(const DevGraph &g, const RowSched &rs, const
         LDPC_FAST_CASE(16, 4, 1)
     }
 #undef LDPC_FAST_CASE
-    return hipErrorInvalidValue;
+    return nullptr;
 }
 
-bool rows_fast_supported(const RowSched &rs, bool f64)
+static bool rows_fast_supported(const RowSched &rs, bool f64)
 {
     if (rs.threads <= 0) return false;
     if (rs.dc != 8 && !(f64 && rs.dc == 16)) return false;
@@ -522,17 +504,15 @@ bool rows_fast_supported(const RowSched &rs, bool f64)
 
 bool rows_fast_f32_ok(const DecodeArgs &a) { return a.variant == V_MS || (a.variant == V_NMS && a.nms_fast); }
 
-hipError_t launch_rows_fast(const DevGraph &g, const RowSched &rs, const DecodeArgs &a, bool f64, int lds_bytes,
-                            unsigned *redo, hipStream_t s, int num_cus)
+static const void *fast_fn(const RowSched &rs, const DecodeArgs &a, bool f64)
 {
     const bool given = a.src == SRC_GIVEN;
-#define LDPC_FAST_SRC(FT, VARV, FD)                                                                         \
-    return given ? launch_fast_shape<FT, VARV, FD, SRC_GIVEN>(g, rs, a, lds_bytes, redo, s, num_cus)        \
-                 : launch_fast_shape<FT, VARV, FD, SRC_PHILOX>(g, rs, a, lds_bytes, redo, s, num_cus);
+#define LDPC_FAST_SRC(FT, VARV, FD) \
+    return given ? fast_shape_fn<FT, VARV, FD, SRC_GIVEN>(rs) : fast_shape_fn<FT, VARV, FD, SRC_PHILOX>(rs);
     if (!f64) {   // fp32: MS, or NMS with the verified reciprocal (rows_fast_f32_ok)
         if (a.variant == V_MS) { LDPC_FAST_SRC(float, V_MS, false) }
         if (a.variant == V_NMS && a.nms_fast) { LDPC_FAST_SRC(float, V_NMS, true) }
-        return hipErrorInvalidValue;
+        return nullptr;
     }
     const bool fdiv = a.variant == V_NMS && markstein_exact_alpha(a.alpha);
     if (a.variant == V_MS) { LDPC_FAST_SRC(double, V_MS, false) }
@@ -540,6 +520,28 @@ hipError_t launch_rows_fast(const DevGraph &g, const RowSched &rs, const DecodeA
     if (fdiv) { LDPC_FAST_SRC(double, V_NMS, true) }
     LDPC_FAST_SRC(double, V_NMS, false)
 #undef LDPC_FAST_SRC
+}
+
+bool plan_rows_fast(const PlanInput &in, LaunchPlan &p)
+{
+    const RowSched &rs = *in.rs;
+    if (!rows_fast_supported(rs, in.f64)) return false;
+    p.kernel = Kernel::rows_fast;
+    p.name = "rows_fast";
+    p.redo = true;
+    p.fn = fast_fn(rs, in.a, in.f64);
+    if (!p.fn) return true;   // launch_rows_fast refuses it
+    const int C = in.f64 ? 1 : 2;
+    int per_cu = std::max(1, occupancy(p.fn, p.threads, p.lds_bytes));
+    if (const int cap = opt(LDPC_OPT_FAST_BPC)) per_cu = std::min(per_cu, cap);   // experiments
+    p.grid = std::min(per_cu * in.num_cus, (in.a.batch + C - 1) / C);
+    return true;
+}
+
+hipError_t launch_rows_fast(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *redo, hipStream_t s)
+{
+    void *args[] = {(void *)&a, (void *)&g, (void *)p.rs, &redo};
+    return launch_fn(p, args, s);
 }
 
 }  // namespace ldpc

@@ -8,5 +8,5 @@ H="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=
 $H -Xclang -target-feature -Xclang -load-store-opt -falign-loops=32 -mllvm -amdgpu-sched-strategy=max-memory-clause \
     -c -o $V/obj_ppst/rows_pp.o ldpcsimulation_amd/csrc/rows_pp.hip 2>/dev/null
 $H -c -o $V/obj_ppst/api.o ldpcsimulation_amd/csrc/api.cpp 2>/dev/null
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libldpc_hip_ppst.so $L/obj/kernels.o $L/obj/rows_fast.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $V/libldpc_hip_ppst.so $L/obj/kernels.o $L/obj/rows.o $L/obj/flood.o $L/obj/layered.o $L/obj/rows_fast.o \
     $V/obj_ppst/rows_pp.o $L/obj/gdbf.o $L/obj/bp.o $L/obj/nb.o $L/obj/nb_api.o $L/obj/nb_graph.o $V/obj_ppst/api.o $L/obj/graph.o

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Summarise the layered kernel's per-wave phase stamps (a -DLDPC_STAMPS build, LayStamps
-in kernels.hip): the last launch's record of $LDPC_STAMPS, averaged over the launch's blocks.
+in layered.hip): the last launch's record of $LDPC_STAMPS, averaged over the launch's blocks.
 
 usage: lay_stamps.py STAMPS_BIN
 """

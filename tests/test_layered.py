@@ -168,7 +168,7 @@ def test_dvbs2_layered_decisions_vs_oracle(gpu_ctx_factory, prec):
 @pytest.mark.parametrize("prec", ["f64", "f32"])
 def test_dvbs2_layered_frames_independent_of_grid(prec):
     """The global layered kernel sizes its grid to the batch (resident codewords inside the
-    Infinity Cache, the same number of codeword rounds on fewer blocks, api.cpp run_kernel):
+    Infinity Cache, the same number of codeword rounds on fewer blocks, layered.hip plan_layered):
     every codeword's result is the same in one 461-frame launch (3 rounds on 154 blocks) as
     in launches of 1, 230 (one round) and 230 frames."""
     native = _native()
