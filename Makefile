@@ -196,7 +196,7 @@ clean:
 # and the CPU oracle under AddressSanitizer + UBSan, driven over code files.
 ASAN_FLAGS = -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=all
 build/host_asan: tests/native/host_asan.cpp $(CSRC)/graph.cpp $(CSRC)/graph.h $(CSRC)/nb_graph.cpp $(CSRC)/nb_graph.h \
-                 $(CSRC)/nb_layout.h $(CSRC)/cli_common.h oracle/ldpc_oracle.c oracle/ldpc_oracle.h
+                 $(CSRC)/nb_layout.h $(CSRC)/cli_common.h $(CSRC)/blob.h oracle/ldpc_oracle.c oracle/ldpc_oracle.h
 	mkdir -p build
 	gcc $(ASAN_FLAGS) -std=c11 -ffp-contract=off -Ioracle -c -o build/ldpc_oracle_asan.o oracle/ldpc_oracle.c
 	g++ $(ASAN_FLAGS) -std=c++17 -Iinclude -I$(CSRC) -Ioracle -o $@ tests/native/host_asan.cpp $(CSRC)/graph.cpp \

@@ -1,9 +1,10 @@
 // api.cpp -- C ABI of libldpc_hip.so (include/ldpc_hip.h).
 //
-// Owns device state (graph upload, counters, staging buffers, events) and
-// maps the reference's per-frame loop onto batched kernel launches. No C++
-// exception crosses the ABI; every HIP failure becomes LDPC_ERR_DEVICE with
-// a message in ldpc_last_error().
+// Owns the binary context's device state (graph and schedule uploads, staging
+// buffers) on top of the runtime it shares with nb_api.cpp (host_rt.h: errors,
+// staging, CtxCore) and maps the reference's per-frame loop onto batched kernel
+// launches. No C++ exception crosses the ABI; every HIP failure becomes
+// LDPC_ERR_DEVICE with a message in ldpc_last_error().
 #include "ldpc_hip.h"
 #include "gdbf.h"
 #include "bp.h"
@@ -12,7 +13,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -23,30 +23,11 @@
 
 #include "graph.h"
 #include "kernels.h"
-#include "check.h"
+#include "host_rt.h"
+
+using namespace ldpc;   // host_rt.h: set_err, HIP_TRY, DevBuf, OutStage, stage_in, CtxCore, Blob
 
 static thread_local std::string g_last_error;
-
-static int set_err(int code, const char *fmt, ...)
-{
-    char buf[1024];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
-#define HIP_TRY(expr)                                                                           \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            (void)hipGetLastError();                                                            \
-            return set_err(LDPC_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
-                           __FILE__, __LINE__);                                                 \
-        }                                                                                       \
-    } while (0)
 
 #ifdef LDPC_CHECK
 namespace ldpc {
@@ -78,53 +59,14 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     return total;
 }
 }  // namespace ldpc
-// checked builds: every launch is synchronised and its indices' record read
-#define LDPC_CHECK_AFTER_LAUNCH(stream)                                                              \
-    do {                                                                                             \
-        char m_[192];                                                                                \
-        const long n_ = ldpc::check_collect((stream), m_, sizeof m_);                                \
-        if (n_ < 0) return set_err(LDPC_ERR_DEVICE, "check_collect: %s", hipGetErrorString((hipError_t)-n_)); \
-        if (n_ > 0) return set_err(LDPC_ERR_DEVICE, "%s; %ld violations", m_, n_);                   \
-    } while (0)
-#else
-#define LDPC_CHECK_AFTER_LAUNCH(stream) ((void)0)
 #endif
 
-struct DevBuf {
-    void *p = nullptr;
-    size_t n = 0;
-    hipError_t ensure(size_t bytes)
-    {
-        if (bytes <= n) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-        hipError_t e = hipMalloc(&p, bytes);
-        if (e == hipSuccess) n = bytes;
-        return e;
-    }
-    void release()
-    {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-struct ldpc_ctx {
-    int device = 0;
+struct ldpc_ctx : CtxCore {
     const ldpc_graph *g = nullptr;
-    int max_batch = 0;
-    int num_cus = 0;
-    hipStream_t own = nullptr, stream = nullptr;
     ldpc::DevGraph dg{};
-    DevBuf graph, counts, hist, y_stage, c_stage, d_stage, fw_stage, cw_table, gscratch, p_stage;
+    DevBuf graph, hist, y_stage, c_stage, d_stage, fw_stage, cw_table, gscratch, p_stage;
     int cw_rows = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t handoff = nullptr;  // orders the launches of a context across ldpc_ctx_set_stream
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
-    bool timed = false;
-    ldpc::Options opts;           // kernel-selection options (ldpc_ctx_set_option), tests and A/B only
     bool has_rs = false;
     ldpc::RowSched rs{};
     DevBuf sched;
@@ -185,35 +127,63 @@ bool option_value_ok(int option, int v)
 }
 }  // namespace ldpc
 
-// Device copy of a host row schedule (graph.cpp build_row_schedule).
+// Device copies of the graph and of the host schedules (graph.cpp): each is one blob of
+// 256-byte aligned sections (blob.h) and a struct of pointers into it.
+template <class T> static const T *section(const DevBuf &buf, size_t off) { return (const T *)((const unsigned char *)buf.p + off); }
+
+static hipError_t upload_graph(const ldpc_graph &g, DevBuf &buf, ldpc::DevGraph &dg)
+{
+    Blob b(256);
+    const size_t o_rc = b.add(g.row_cols), o_rd = b.add(g.row_deg), o_cp = b.add(g.col_ptr),
+                 o_cr = b.add(g.col_refs.data(), sizeof(uint32_t) * g.col_refs.size(), sizeof(uint32_t) * ((size_t)g.E + 1));
+    const hipError_t e = upload(b, buf);
+    if (e != hipSuccess) return e;
+    dg = {g.N, g.M, g.maxdc > 0 ? g.maxdc : 1, section<int32_t>(buf, o_rc), section<uint8_t>(buf, o_rd),
+          section<int32_t>(buf, o_cp), section<uint32_t>(buf, o_cr)};
+    return hipSuccess;
+}
+
 static hipError_t upload_row_sched(const ldpc::RowSchedule &hs, DevBuf &buf, ldpc::RowSched &rs)
 {
-    auto al = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_cc = al(2 * hs.cn_cols.size()), b_cp = al(2 * hs.cn_pos.size()), b_cd = al(hs.cn_deg.size()),
-                 b_vc = al(2 * hs.vn_col.size()), b_vi = al(4 * hs.vn_info.size());
-    hipError_t e = buf.ensure(b_cc + b_cp + b_cd + b_vc + b_vi);
+    Blob b(256);
+    const size_t o_cc = b.add(hs.cn_cols), o_cp = b.add(hs.cn_pos), o_cd = b.add(hs.cn_deg), o_vc = b.add(hs.vn_col),
+                 o_vi = b.add(hs.vn_info);
+    const hipError_t e = upload(b, buf);
     if (e != hipSuccess) return e;
-    unsigned char *sb = (unsigned char *)buf.p;
-    const std::pair<const void *, size_t> parts[] = {{hs.cn_cols.data(), 2 * hs.cn_cols.size()},
-                                                     {hs.cn_pos.data(), 2 * hs.cn_pos.size()},
-                                                     {hs.cn_deg.data(), hs.cn_deg.size()},
-                                                     {hs.vn_col.data(), 2 * hs.vn_col.size()},
-                                                     {hs.vn_info.data(), 4 * hs.vn_info.size()}};
-    const size_t offs[] = {0, b_cc, b_cc + b_cp, b_cc + b_cp + b_cd, b_cc + b_cp + b_cd + b_vc};
-    for (int i = 0; i < 5; ++i)
-        if (parts[i].second && (e = hipMemcpy(sb + offs[i], parts[i].first, parts[i].second, hipMemcpyHostToDevice)) != hipSuccess)
-            return e;
-    rs.threads = hs.threads;
-    rs.cpt = hs.cpt;
-    rs.dc = hs.dc;
-    rs.e_pad = hs.e_pad;
-    rs.rpt = hs.rpt;
-    rs.dc_low = hs.dc_low;
-    rs.cn_cols = (const uint16_t *)sb;
-    rs.cn_pos = (const uint16_t *)(sb + offs[1]);
-    rs.cn_deg = (const uint8_t *)(sb + offs[2]);
-    rs.vn_col = (const uint16_t *)(sb + offs[3]);
-    rs.vn_info = (const uint32_t *)(sb + offs[4]);
+    rs = {hs.threads, hs.cpt, hs.dc, hs.e_pad, hs.rpt, hs.dc_low, section<uint16_t>(buf, o_cc),
+          section<uint16_t>(buf, o_cp), section<uint8_t>(buf, o_cd), section<uint16_t>(buf, o_vc),
+          section<uint32_t>(buf, o_vi)};
+    return hipSuccess;
+}
+
+static hipError_t upload_flood_sched(const ldpc_graph &g, const ldpc::FloodSchedule &fh, DevBuf &buf, ldpc::FloodSched &fs)
+{
+    // element -> (row, position) of the c2v layout: the packed-message bit phase
+    // (flood.hip k_flood_bit_packed) rebuilds a message from its row's state
+    std::vector<uint32_t> eref((size_t)fh.e_pad + 64, 0);
+    for (int i = 0; i < fh.M_pad; ++i)
+        for (int k = 0; k < fh.rdeg[i]; ++k)
+            eref[fh.sq[(size_t)k * fh.M_pad + i]] = ((uint32_t)i << 5) | (uint32_t)k;
+    Blob b(256);
+    const size_t o_sp = b.add(fh.sp), o_sq = b.add(fh.sq), o_rd = b.add(fh.rdeg), o_pb = b.add(fh.pos_of_bit),
+                 o_ba = b.add(fh.bit_at), o_pd = b.add(fh.pdeg), o_gb = b.add(fh.gbase), o_er = b.add(eref);
+    const hipError_t e = upload(b, buf);
+    if (e != hipSuccess) return e;
+    fs = {fh.M_pad, fh.dc, fh.ngroups, fh.e_pad, g.maxdv, section<int32_t>(buf, o_sp), section<int32_t>(buf, o_sq),
+          section<uint8_t>(buf, o_rd), section<int32_t>(buf, o_pb), section<int32_t>(buf, o_ba),
+          section<uint8_t>(buf, o_pd), section<int32_t>(buf, o_gb), section<uint32_t>(buf, o_er)};
+    return hipSuccess;
+}
+
+static hipError_t upload_layer_sched(const ldpc::LayerSchedule &lh, DevBuf &buf, ldpc::LayerSched &ls)
+{
+    Blob b(256);
+    const size_t o_lp = b.add(lh.lptr), o_sp = b.add(lh.sp), o_rd = b.add(lh.rdeg), o_pb = b.add(lh.pos_of_bit);
+    const hipError_t e = upload(b, buf);
+    if (e != hipSuccess) return e;
+    ls = {(int)lh.lptr.size() - 1, 0, lh.M_pad, section<int32_t>(buf, o_lp), section<int32_t>(buf, o_sp),
+          section<uint8_t>(buf, o_rd), section<int32_t>(buf, o_pb)};
+    for (int L = 0; L < ls.nlayers; ++L) ls.max_layer = std::max(ls.max_layer, lh.lptr[L + 1] - lh.lptr[L]);
     return hipSuccess;
 }
 
@@ -359,20 +329,67 @@ int ldpc_device_count(int *n)
 static void ctx_free(ldpc_ctx *c)
 {
     if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
-    for (DevBuf *b : {&c->graph, &c->counts, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage,
-                      &c->cw_table, &c->gscratch, &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage,
-                      &c->redo})
-        b->release();
-    if (c->ev0) (void)hipEventDestroy(c->ev0);
-    if (c->ev1) (void)hipEventDestroy(c->ev1);
-    if (c->handoff) (void)hipEventDestroy(c->handoff);
+    c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
+                &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
     if (c->aux.join) (void)hipEventDestroy(c->aux.join);
     if (c->aux.s) (void)hipStreamDestroy(c->aux.s);
-    if (c->own) (void)hipStreamDestroy(c->own);
     delete c;
+}
+
+// Everything ldpc_ctx_create puts on the device; on failure the caller frees the context.
+static int ctx_init(ldpc_ctx *c, int device, const ldpc_graph *g, int max_batch)
+{
+    c->g = g;
+    RC_TRY(c->init(device, max_batch));
+    HIP_TRY(hipStreamCreateWithFlags(&c->aux.s, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&c->aux.fork, hipEventDisableTiming));
+    HIP_TRY(hipEventCreateWithFlags(&c->aux.join, hipEventDisableTiming));
+    HIP_TRY(upload_graph(*g, c->graph, c->dg));
+
+    // Row-parallel schedule (the throughput kernel) when the graph fits it.
+    // Rows per thread: 1 up to 512 rows (512-thread blocks), 2 up to 1024 rows
+    // (512 threads, two blocks per CU: their barriers overlap; measured 1.13x
+    // over one 1024-thread block with 1 row per thread on the N=1944 code).
+    const int rpt = g->M <= 512 ? 1 : 2;
+    int threads = ((((g->M + rpt - 1) / rpt) + 63) / 64) * 64;
+    if (threads < 64) threads = 64;
+    int dc = 0, cpt = 0;
+    for (int d : ldpc::kRowsDc)
+        if (!dc && g->maxdc <= d) dc = d;
+    static const int cpt_for_rpt[][3] = {{0, 0, 0}, {2, 4, 0}, {4, 0, 0}};
+    for (int q : cpt_for_rpt[rpt])
+        if (q && !cpt && (long)(threads / 64) * q >= (g->N + 63) / 64) cpt = q;
+    ldpc::RowSchedule hs;
+    if (threads <= ldpc::kRowsMaxThreadsForRpt[rpt] && dc && cpt &&
+        ldpc::build_row_schedule(*g, threads, cpt, dc, rpt, hs).empty()) {
+        HIP_TRY(upload_row_sched(hs, c->sched, c->rs));
+        c->has_rs = true;
+        // the ping-pong kernel's copy: degree-7 rows on the younger check waves (graph.h pp_row_slots)
+        const std::vector<int> slots = ldpc::pp_row_slots(*g, threads, 7);
+        ldpc::RowSchedule hp;
+        if (rpt == 2 && dc == 8 && cpt == 4 && !slots.empty() &&
+            ldpc::build_row_schedule(*g, threads, cpt, dc, rpt, hp, &slots).empty()) {
+            hp.dc_low = 7;
+            HIP_TRY(upload_row_sched(hp, c->sched_pp, c->rs_pp));
+            c->has_rs_pp = true;
+        }
+    }
+    // Flood schedule (global-memory kernel for codes whose state exceeds LDS; also
+    // selectable with LDPC_OPT_KERNEL for tests), and the layered schedule built on it.
+    ldpc::FloodSchedule fh;
+    if (ldpc::build_flood_schedule(*g, fh).empty()) {
+        HIP_TRY(upload_flood_sched(*g, fh, c->fsched, c->fs));
+        c->has_fs = true;
+        ldpc::LayerSchedule lh;
+        if (fh.dc <= ldpc::kPackedMaxDc && ldpc::build_layers(*g, fh, lh).empty()) {
+            HIP_TRY(upload_layer_sched(lh, c->lsched, c->ls));
+            c->has_ls = true;
+        }
+    }
+    HIP_TRY(c->hist.ensure(sizeof(unsigned long long) * (size_t)g->N));
+    HIP_TRY(hipMemset(c->hist.p, 0, c->hist.n));
+    return LDPC_OK;
 }
 
 int ldpc_ctx_create(int device, const ldpc_graph *g, int max_batch, ldpc_ctx **out)
@@ -385,180 +402,21 @@ int ldpc_ctx_create(int device, const ldpc_graph *g, int max_batch, ldpc_ctx **o
     if (device < 0 || device >= ndev) return set_err(LDPC_ERR_INVALID, "device %d of %d", device, ndev);
     ldpc_ctx *c = new (std::nothrow) ldpc_ctx();
     if (!c) return set_err(LDPC_ERR_NOMEM, "ctx allocation failed");
-    c->device = device;
-    c->g = g;
-    c->max_batch = max_batch;
-    auto fail = [&](int rc) {
+    const int rc = ctx_init(c, device, g, max_batch);
+    if (rc) {
         ctx_free(c);
         return rc;
-    };
-    hipError_t e;
-#define CTX_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        e = (expr);                                                                                     \
-        if (e != hipSuccess) {                                                                          \
-            (void)hipGetLastError();                                                                    \
-            return fail(set_err(LDPC_ERR_DEVICE, "%s failed: %s", #expr, hipGetErrorString(e)));       \
-        }                                                                                               \
-    } while (0)
-    CTX_TRY(hipSetDevice(device));
-    hipDeviceProp_t prop;
-    CTX_TRY(hipGetDeviceProperties(&prop, device));
-    c->num_cus = prop.multiProcessorCount;
-    CTX_TRY(hipStreamCreateWithFlags(&c->own, hipStreamNonBlocking));
-    c->stream = c->own;
-    CTX_TRY(hipEventCreate(&c->ev0));
-    CTX_TRY(hipEventCreate(&c->ev1));
-    CTX_TRY(hipStreamCreateWithFlags(&c->aux.s, hipStreamNonBlocking));
-    CTX_TRY(hipEventCreateWithFlags(&c->aux.fork, hipEventDisableTiming));
-    CTX_TRY(hipEventCreateWithFlags(&c->aux.join, hipEventDisableTiming));
-
-    // Graph upload: one allocation, 256-B aligned sections.
-    const int dcs = g->maxdc > 0 ? g->maxdc : 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t s_rc = al(sizeof(int32_t) * (size_t)g->M * dcs), s_rd = al((size_t)g->M),
-                 s_cp = al(sizeof(int32_t) * (size_t)(g->N + 1)), s_cr = al(sizeof(uint32_t) * (size_t)(g->E + 1));
-    CTX_TRY(c->graph.ensure(s_rc + s_rd + s_cp + s_cr));
-    unsigned char *gb = (unsigned char *)c->graph.p;
-    CTX_TRY(hipMemcpy(gb, g->row_cols.data(), sizeof(int32_t) * g->row_cols.size(), hipMemcpyHostToDevice));
-    CTX_TRY(hipMemcpy(gb + s_rc, g->row_deg.data(), g->row_deg.size(), hipMemcpyHostToDevice));
-    CTX_TRY(hipMemcpy(gb + s_rc + s_rd, g->col_ptr.data(), sizeof(int32_t) * g->col_ptr.size(),
-                      hipMemcpyHostToDevice));
-    if (g->E > 0)
-        CTX_TRY(hipMemcpy(gb + s_rc + s_rd + s_cp, g->col_refs.data(), sizeof(uint32_t) * g->col_refs.size(),
-                          hipMemcpyHostToDevice));
-    c->dg.N = g->N;
-    c->dg.M = g->M;
-    c->dg.dcs = dcs;
-    c->dg.row_cols = (const int32_t *)gb;
-    c->dg.row_deg = (const uint8_t *)(gb + s_rc);
-    c->dg.col_ptr = (const int32_t *)(gb + s_rc + s_rd);
-    c->dg.col_refs = (const uint32_t *)(gb + s_rc + s_rd + s_cp);
-
-    // Row-parallel schedule (the throughput kernel) when the graph fits it.
-    {
-        // Rows per thread: 1 up to 512 rows (512-thread blocks), 2 up to 1024 rows
-        // (512 threads, two blocks per CU: their barriers overlap; measured 1.13x
-        // over one 1024-thread block with 1 row per thread on the N=1944 code).
-        const int rpt = g->M <= 512 ? 1 : 2;
-        int threads = ((((g->M + rpt - 1) / rpt) + 63) / 64) * 64;
-        if (threads < 64) threads = 64;
-        int dc = 0, cpt = 0;
-        for (int d : ldpc::kRowsDc)
-            if (!dc && g->maxdc <= d) dc = d;
-        static const int cpt_for_rpt[][3] = {{0, 0, 0}, {2, 4, 0}, {4, 0, 0}};
-        for (int q : cpt_for_rpt[rpt])
-            if (q && !cpt && (long)(threads / 64) * q >= (g->N + 63) / 64) cpt = q;
-        ldpc::RowSchedule hs;
-        if (threads <= ldpc::kRowsMaxThreadsForRpt[rpt] && dc && cpt &&
-            ldpc::build_row_schedule(*g, threads, cpt, dc, rpt, hs).empty()) {
-            CTX_TRY(upload_row_sched(hs, c->sched, c->rs));
-            c->has_rs = true;
-            // the ping-pong kernel's copy: degree-7 rows on the younger check waves (graph.h pp_row_slots)
-            const std::vector<int> slots = ldpc::pp_row_slots(*g, threads, 7);
-            ldpc::RowSchedule hp;
-            if (rpt == 2 && dc == 8 && cpt == 4 && !slots.empty() &&
-                ldpc::build_row_schedule(*g, threads, cpt, dc, rpt, hp, &slots).empty()) {
-                hp.dc_low = 7;
-                CTX_TRY(upload_row_sched(hp, c->sched_pp, c->rs_pp));
-                c->has_rs_pp = true;
-            }
-        }
     }
-    // Flood schedule (global-memory kernel for codes whose state exceeds LDS;
-    // also selectable with LDPC_KERNEL=flood for tests).
-    {
-        ldpc::FloodSchedule fh;
-        if (ldpc::build_flood_schedule(*g, fh).empty()) {
-            const size_t n_sp = fh.sp.size(), n_rd = fh.rdeg.size(), n_pb = fh.pos_of_bit.size(),
-                         n_ba = fh.bit_at.size(), n_pd = fh.pdeg.size(), n_gb = fh.gbase.size();
-            const size_t o_sq = al(4 * n_sp), o_rd = o_sq + al(4 * n_sp), o_pb = o_rd + al(n_rd),
-                         o_ba = o_pb + al(4 * n_pb), o_pd = o_ba + al(4 * n_ba), o_gb = o_pd + al(n_pd),
-                         o_er = o_gb + al(4 * n_gb), n_er = (size_t)fh.e_pad + 64, tot = o_er + al(4 * n_er);
-            // element -> (row, position) of the c2v layout: the packed-message bit phase
-            // (flood.hip k_flood_bit_packed) rebuilds a message from its row's state
-            std::vector<uint32_t> eref(n_er, 0);
-            for (int i = 0; i < fh.M_pad; ++i)
-                for (int k = 0; k < fh.rdeg[i]; ++k)
-                    eref[fh.sq[(size_t)k * fh.M_pad + i]] = ((uint32_t)i << 5) | (uint32_t)k;
-            CTX_TRY(c->fsched.ensure(tot));
-            unsigned char *fb = (unsigned char *)c->fsched.p;
-            CTX_TRY(hipMemcpy(fb, fh.sp.data(), 4 * n_sp, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_sq, fh.sq.data(), 4 * n_sp, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_rd, fh.rdeg.data(), n_rd, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_pb, fh.pos_of_bit.data(), 4 * n_pb, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_ba, fh.bit_at.data(), 4 * n_ba, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_pd, fh.pdeg.data(), n_pd, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_gb, fh.gbase.data(), 4 * n_gb, hipMemcpyHostToDevice));
-            CTX_TRY(hipMemcpy(fb + o_er, eref.data(), 4 * n_er, hipMemcpyHostToDevice));
-            c->fs.M_pad = fh.M_pad;
-            c->fs.dc = fh.dc;
-            c->fs.ngroups = fh.ngroups;
-            c->fs.e_pad = fh.e_pad;
-            c->fs.dv = g->maxdv;
-            c->fs.sp = (const int32_t *)fb;
-            c->fs.sq = (const int32_t *)(fb + o_sq);
-            c->fs.rdeg = (const uint8_t *)(fb + o_rd);
-            c->fs.pos_of_bit = (const int32_t *)(fb + o_pb);
-            c->fs.bit_at = (const int32_t *)(fb + o_ba);
-            c->fs.pdeg = (const uint8_t *)(fb + o_pd);
-            c->fs.gbase = (const int32_t *)(fb + o_gb);
-            c->fs.eref = (const uint32_t *)(fb + o_er);
-            c->has_fs = true;
-            ldpc::LayerSchedule lh;
-            if (fh.dc <= ldpc::kPackedMaxDc && ldpc::build_layers(*g, fh, lh).empty()) {
-                const size_t n_lp = lh.lptr.size(), n_sp = lh.sp.size(), n_rd = lh.rdeg.size(),
-                             n_pb = lh.pos_of_bit.size();
-                const size_t o_sp = al(4 * n_lp), o_rd = o_sp + al(4 * n_sp), o_pb = o_rd + al(n_rd),
-                             tot = o_pb + al(4 * n_pb);
-                CTX_TRY(c->lsched.ensure(tot));
-                unsigned char *lb = (unsigned char *)c->lsched.p;
-                CTX_TRY(hipMemcpy(lb, lh.lptr.data(), 4 * n_lp, hipMemcpyHostToDevice));
-                CTX_TRY(hipMemcpy(lb + o_sp, lh.sp.data(), 4 * n_sp, hipMemcpyHostToDevice));
-                CTX_TRY(hipMemcpy(lb + o_rd, lh.rdeg.data(), n_rd, hipMemcpyHostToDevice));
-                CTX_TRY(hipMemcpy(lb + o_pb, lh.pos_of_bit.data(), 4 * n_pb, hipMemcpyHostToDevice));
-                c->ls.pos_of_bit = (const int32_t *)(lb + o_pb);
-                c->ls.nlayers = (int)n_lp - 1;
-                c->ls.M_pad = lh.M_pad;
-                c->ls.lptr = (const int32_t *)lb;
-                c->ls.sp = (const int32_t *)(lb + o_sp);
-                c->ls.rdeg = (const uint8_t *)(lb + o_rd);
-                for (int L = 0; L < c->ls.nlayers; ++L)
-                    c->ls.max_layer = std::max(c->ls.max_layer, lh.lptr[L + 1] - lh.lptr[L]);
-                c->has_ls = true;
-            }
-        }
-    }
-    CTX_TRY(c->counts.ensure(8 * sizeof(unsigned long long)));
-    CTX_TRY(hipMemset(c->counts.p, 0, c->counts.n));
-    CTX_TRY(c->hist.ensure(sizeof(unsigned long long) * (size_t)g->N));
-    CTX_TRY(hipMemset(c->hist.p, 0, c->hist.n));
-#undef CTX_TRY
     *out = c;
     return LDPC_OK;
 }
 
-int ldpc_ctx_set_stream(ldpc_ctx *c, void *s)
-{
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    const hipStream_t ns = s ? (hipStream_t)s : c->own;
-    if (ns != c->stream) {
-        // The launches of one context share its counters (the GDBF/EMS codeword ticket
-        // included), staging and re-decode buffers: the new stream starts after everything
-        // already queued on the old one, so launches never overlap across a stream change.
-        HIP_TRY(hipSetDevice(c->device));
-        if (!c->handoff) HIP_TRY(hipEventCreateWithFlags(&c->handoff, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->handoff, c->stream));
-        HIP_TRY(hipStreamWaitEvent(ns, c->handoff, 0));
-    }
-    c->stream = ns;
-    return LDPC_OK;
-}
+int ldpc_ctx_set_stream(ldpc_ctx *c, void *s) { return c ? c->set_stream(s) : set_err(LDPC_ERR_INVALID, "ctx is null"); }
 
 int ldpc_ctx_synchronize(ldpc_ctx *c)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LDPC_OK;
 }
@@ -567,13 +425,7 @@ void ldpc_ctx_destroy(ldpc_ctx *c) { ctx_free(c); }
 
 int ldpc_ctx_set_option(ldpc_ctx *c, int option, int value)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    if (!ldpc::option_value_ok(option, value))
-        return set_err(LDPC_ERR_INVALID, "option %d: unknown, or value %d out of range", option, value);
-    if (ldpc::option_is_ems(option))
-        return set_err(LDPC_ERR_INVALID, "option %d is an EMS option (ldpc_nb_ctx_set_option)", option);
-    c->opts.v[option] = value;
-    return LDPC_OK;
+    return c ? c->set_option(option, value, false) : set_err(LDPC_ERR_INVALID, "ctx is null");
 }
 
 int ldpc_ctx_get_option(const ldpc_ctx *c, int option, int *value)
@@ -585,18 +437,6 @@ int ldpc_ctx_get_option(const ldpc_ctx *c, int option, int *value)
 }
 
 // ----------------------------------------------------------------- helpers
-static bool is_device_ptr(const void *p)
-{
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
 static int check_cfg(const ldpc_ctx *c, const ldpc_decoder_cfg *cfg)
 {
     if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
@@ -711,7 +551,7 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
         a.stamps = (unsigned long long *)stamp_buf.p;
     }
 #endif
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    RC_TRY(c->begin_launch());
     c->last_fast = p.redo;
     if (p.redo) HIP_TRY(hipMemsetAsync(c->redo.p, 0, sizeof(unsigned), c->stream));
     switch (p.kernel) {
@@ -734,8 +574,7 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
     }
     // the exact re-decode of any codeword whose fast-path premise failed
     if (p.redo) HIP_TRY(ldpc::launch_redo(c->dg, a, f64, (const unsigned *)c->redo.p, c->stream, c->num_cus));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
+    RC_TRY(c->end_launch());
 #ifdef LDPC_STAMPS
     if (stamp_path) {
         std::vector<unsigned long long> h(8192 * 4);
@@ -747,86 +586,18 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
         }
     }
 #endif
-    LDPC_CHECK_AFTER_LAUNCH(c->stream);
     return LDPC_OK;
 }
-
-static int read_counts(ldpc_ctx *c, ldpc_counts *out, int reset)
-{
-    unsigned long long h[8];
-    HIP_TRY(hipMemcpyAsync(h, c->counts.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    if (out) {
-        out->bit_err = (int64_t)h[0];
-        out->frame_err = (int64_t)h[1];
-        out->uncoded_bit_err = (int64_t)h[2];
-        out->frames = (int64_t)h[3];
-        out->iters = (int64_t)h[4];
-        out->syndrome_fail = (int64_t)h[5];
-    }
-    if (reset) HIP_TRY(hipMemsetAsync(c->counts.p, 0, c->counts.n, c->stream));
-    return LDPC_OK;
-}
-
-static void accumulate(ldpc_counts *acc, const ldpc_counts &d)
-{
-    acc->bit_err += d.bit_err;
-    acc->frame_err += d.frame_err;
-    acc->uncoded_bit_err += d.uncoded_bit_err;
-    acc->frames += d.frames;
-    acc->iters += d.iters;
-    acc->syndrome_fail += d.syndrome_fail;
-}
-
-static int counts_delta(ldpc_ctx *c, const ldpc_counts &before, ldpc_counts *acc)
-{
-    ldpc_counts after;
-    int rc = read_counts(c, &after, 0);
-    if (rc) return rc;
-    if (acc) {
-        ldpc_counts d;
-        d.bit_err = after.bit_err - before.bit_err;
-        d.frame_err = after.frame_err - before.frame_err;
-        d.uncoded_bit_err = after.uncoded_bit_err - before.uncoded_bit_err;
-        d.frames = after.frames - before.frames;
-        d.iters = after.iters - before.iters;
-        d.syndrome_fail = after.syndrome_fail - before.syndrome_fail;
-        accumulate(acc, d);
-    }
-    return LDPC_OK;
-}
-
-// An output the caller may hold on the host or on the device: the kernel writes dev (the
-// caller's own pointer, or the staging buffer when that is host memory; null: not wanted),
-// and fetch() copies a staged output back once the launch is queued.
-struct OutStage {
-    void *user = nullptr, *dev = nullptr;
-    size_t bytes = 0;
-    hipError_t bind(void *out, DevBuf &stage, size_t n)
-    {
-        user = dev = out;
-        bytes = n;
-        if (!out || is_device_ptr(out)) return hipSuccess;
-        const hipError_t e = stage.ensure(n);
-        dev = stage.p;
-        return e;
-    }
-    hipError_t fetch(hipStream_t s) const
-    {
-        return dev == user ? hipSuccess : hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s);
-    }
-};
 
 // ----------------------------------------------------------------- decode
 int ldpc_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_decoder_cfg *cfg, const int8_t *cw,
                       int8_t *d_out, ldpc_frame_result *frame_weights, ldpc_counts *counts)
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
-    int rc = check_cfg(c, cfg);
-    if (rc) return rc;
+    RC_TRY(check_cfg(c, cfg));
     if (batch <= 0 || batch > c->max_batch)
         return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     if (cfg->variant == LDPC_BP && !(cfg->n0 > 0)) return set_err(LDPC_ERR_INVALID, "BP needs cfg->n0 > 0");
     const bool f64 = cfg->precision == LDPC_F64;
     const int N = c->g->N;
@@ -836,40 +607,20 @@ int ldpc_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_decoder_
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, batch);
     a.src = ldpc::SRC_GIVEN;
-    {
-        const int nrc = nms_setup(c, cfg, a);
-        if (nrc) return nrc;
-    }
-    // Inputs: stage host buffers.
-    if (is_device_ptr(y)) {
-        a.y = y;
-    } else {
-        HIP_TRY(c->y_stage.ensure(ybytes));
-        HIP_TRY(hipMemcpyAsync(c->y_stage.p, y, ybytes, hipMemcpyHostToDevice, c->stream));
-        a.y = c->y_stage.p;
-    }
-    if (cw) {
-        if (is_device_ptr(cw)) {
-            a.c = cw;
-        } else {
-            HIP_TRY(c->c_stage.ensure(nbytes));
-            HIP_TRY(hipMemcpyAsync(c->c_stage.p, cw, nbytes, hipMemcpyHostToDevice, c->stream));
-            a.c = (const int8_t *)c->c_stage.p;
-        }
-    }
+    RC_TRY(nms_setup(c, cfg, a));
+    HIP_TRY(stage_in(y, ybytes, c->y_stage, c->stream, a.y));
+    HIP_TRY(stage_in(cw, nbytes, c->c_stage, c->stream, a.c));
     OutStage d, w;
     HIP_TRY(d.bind(d_out, c->d_stage, nbytes));
     HIP_TRY(w.bind(frame_weights, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
     a.d_out = (int8_t *)d.dev;
     a.frame_res = (int4 *)w.dev;
-    ldpc_counts before;
-    rc = read_counts(c, &before, 0);
-    if (rc) return rc;
-    rc = run_kernel(c, a, f64, cfg->schedule);
-    if (rc) return rc;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(run_kernel(c, a, f64, cfg->schedule));
     HIP_TRY(d.fetch(c->stream));
     HIP_TRY(w.fetch(c->stream));
-    return counts_delta(c, before, counts);
+    return c->counts_since(before, counts);
 }
 
 // ----------------------------------------------------------------- Monte-Carlo
@@ -877,7 +628,7 @@ int ldpc_sim_set_codewords(ldpc_ctx *c, const uint8_t *bits, int rows)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     if (rows < 0 || (rows > 0 && !bits)) return set_err(LDPC_ERR_INVALID, "bad codeword table");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     c->cw_rows = 0;
     if (rows == 0) return LDPC_OK;
     const size_t n = (size_t)rows * c->g->N;
@@ -897,19 +648,15 @@ static int sim_launch_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_dec
                            void *y_out_dev, int8_t *d_out_dev)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    int rc = check_cfg(c, cfg);
-    if (rc) return rc;
+    RC_TRY(check_cfg(c, cfg));
     if (batch <= 0 || batch > c->max_batch)
         return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
     if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, batch);
     a.src = ldpc::SRC_PHILOX;
-    {
-        const int nrc = nms_setup(c, cfg, a);
-        if (nrc) return nrc;
-    }
+    RC_TRY(nms_setup(c, cfg, a));
     const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // :146
     a.sigma = std::sqrt(N0 / 2.0);                            // :147
     if (cfg->variant == LDPC_BP) a.n0 = N0;                   // 4*y/N0 (decodeBP.cpp:104,188)
@@ -935,14 +682,14 @@ int ldpc_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cf
 int ldpc_ctx_read_counts(ldpc_ctx *c, ldpc_counts *out, int reset)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    HIP_TRY(hipSetDevice(c->device));
-    return read_counts(c, out, reset);
+    RC_TRY(c->enter());
+    return c->read_counts(out, reset);
 }
 
 int ldpc_ctx_read_histogram(ldpc_ctx *c, int64_t *out, int reset)
 {
     if (!c || !out) return set_err(LDPC_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     HIP_TRY(hipMemcpyAsync(out, c->hist.p, c->hist.n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     if (reset) HIP_TRY(hipMemsetAsync(c->hist.p, 0, c->hist.n, c->stream));
@@ -955,27 +702,24 @@ static int sim_sync_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decod
                          ldpc_frame_result *frames, ldpc_counts *accum)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    int rc = check_cfg(c, cfg);
-    if (rc) return rc;
+    RC_TRY(check_cfg(c, cfg));
     if (batch <= 0 || batch > c->max_batch)
         return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     const size_t nb = (size_t)batch * c->g->N;
     const size_t ybytes = nb * (cfg->precision == LDPC_F64 ? 8 : 4);
-    ldpc_counts before;
-    rc = read_counts(c, &before, 0);
-    if (rc) return rc;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
     OutStage w, y, d;
     HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
     HIP_TRY(y.bind(y_out, c->y_stage, ybytes));
     HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    rc = sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev, y.dev,
-                         (int8_t *)d.dev);
-    if (rc) return rc;
+    RC_TRY(sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev, y.dev,
+                           (int8_t *)d.dev));
     HIP_TRY(w.fetch(c->stream));
     HIP_TRY(y.fetch(c->stream));
     HIP_TRY(d.fetch(c->stream));
-    return counts_delta(c, before, accum);
+    return c->counts_since(before, accum);
 }
 
 int ldpc_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
@@ -993,25 +737,18 @@ int ldpc_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg
 
 int ldpc_ctx_last_kernel_ms(ldpc_ctx *c, float *ms)
 {
-    if (!c || !ms) return set_err(LDPC_ERR_INVALID, "null argument");
-    if (!c->timed) return set_err(LDPC_ERR_INVALID, "no kernel launched yet");
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipEventSynchronize(c->ev1));
-    HIP_TRY(hipEventElapsedTime(ms, c->ev0, c->ev1));
-    return LDPC_OK;
+    return c ? c->last_kernel_ms(ms) : set_err(LDPC_ERR_INVALID, "null argument");
 }
 
 // The plan of cfg as the info calls report it (a one-codeword batch, no sample source).
 static int info_plan(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, ldpc::LaunchPlan &p)
 {
     if (!c || !cfg) return set_err(LDPC_ERR_INVALID, "null argument");
-    HIP_TRY(hipSetDevice(c->device));
-    int rc = check_cfg(c, cfg);
-    if (rc) return rc;
+    RC_TRY(c->enter());
+    RC_TRY(check_cfg(c, cfg));
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, 1);
-    rc = nms_setup(c, cfg, a);   // fp32 NMS: whether the verified reciprocal (and so the fast kernels) applies
-    if (rc) return rc;
+    RC_TRY(nms_setup(c, cfg, a));   // fp32 NMS: whether the verified reciprocal (and so the fast kernels) applies
     p = build_plan(c, a, cfg->precision == LDPC_F64, cfg->schedule);
     return LDPC_OK;
 }
@@ -1020,8 +757,7 @@ int ldpc_ctx_row_sched_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *i
 {
     if (!info) return set_err(LDPC_ERR_INVALID, "null argument");
     ldpc::LaunchPlan p;
-    const int rc = info_plan(c, cfg, p);
-    if (rc) return rc;
+    RC_TRY(info_plan(c, cfg, p));
     if (!p.rs) return set_err(LDPC_ERR_UNSUPPORTED, "the row kernel does not decode this cfg (kernel %s)", p.name);
     const ldpc::RowSched &rs = *p.rs;
     info[0] = rs.threads;
@@ -1046,7 +782,7 @@ int ldpc_ctx_redo_count(ldpc_ctx *c, int64_t *n)
     if (!c || !n) return set_err(LDPC_ERR_INVALID, "null argument");
     *n = 0;
     if (!c->last_fast || !c->redo.p) return LDPC_OK;
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     unsigned h = 0;
     HIP_TRY(hipMemcpyAsync(&h, c->redo.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1058,8 +794,7 @@ int ldpc_ctx_kernel_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, char *name, i
                          int *bpc)
 {
     ldpc::LaunchPlan p;
-    const int rc = info_plan(c, cfg, p);
-    if (rc) return rc;
+    RC_TRY(info_plan(c, cfg, p));
     if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", p.name);
     if (lds_bytes) *lds_bytes = p.lds_bytes;
     if (bpc) *bpc = p.blocks_per_cu;
@@ -1117,84 +852,55 @@ static int gdbf_run(ldpc_ctx *c, const ldpc::GdbfArgs &a, bool f64)
         slots = std::min(a.batch, 2 * c->num_cus);
         HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
     }
-    HIP_TRY(hipEventRecord(c->ev0, c->stream));
+    RC_TRY(c->begin_launch());
     HIP_TRY(ldpc::gdbf_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
-    HIP_TRY(hipEventRecord(c->ev1, c->stream));
-    c->timed = true;
-    LDPC_CHECK_AFTER_LAUNCH(c->stream);
-    return LDPC_OK;
+    return c->end_launch();
 }
 
 int ldpc_gdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_gdbf_cfg *cfg,
                            const int8_t *cw, int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
-    int rc = gdbf_check_cfg(cfg);
-    if (rc) return rc;
+    RC_TRY(gdbf_check_cfg(cfg));
     if (batch <= 0 || batch > c->max_batch)
         return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
     if ((cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB)) && !pert)
         return set_err(LDPC_ERR_INVALID, "NOISE / QPROB need pert");
     if ((cfg->flags & LDPC_GDBF_QPROB) && !(cfg->qsigma > 0)) return set_err(LDPC_ERR_INVALID, "QPROB needs qsigma > 0");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
     const int N = c->g->N;
     const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
     ldpc::GdbfArgs a;
     gdbf_fill(a, c, cfg, batch);
     a.src = ldpc::SRC_GIVEN;
-    if (is_device_ptr(y)) {
-        a.y = y;
-    } else {
-        HIP_TRY(c->y_stage.ensure(nb * fsz));
-        HIP_TRY(hipMemcpyAsync(c->y_stage.p, y, nb * fsz, hipMemcpyHostToDevice, c->stream));
-        a.y = c->y_stage.p;
-    }
-    if (cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB)) {
-        const size_t pb = nb * (size_t)cfg->T * fsz;
-        if (is_device_ptr(pert)) {
-            a.pert = pert;
-        } else {
-            HIP_TRY(c->p_stage.ensure(pb));
-            HIP_TRY(hipMemcpyAsync(c->p_stage.p, pert, pb, hipMemcpyHostToDevice, c->stream));
-            a.pert = c->p_stage.p;
-        }
-    }
-    if (cw) {
-        if (is_device_ptr(cw)) {
-            a.c = cw;
-        } else {
-            HIP_TRY(c->c_stage.ensure(nb));
-            HIP_TRY(hipMemcpyAsync(c->c_stage.p, cw, nb, hipMemcpyHostToDevice, c->stream));
-            a.c = (const int8_t *)c->c_stage.p;
-        }
-    }
+    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
+    if (cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB))
+        HIP_TRY(stage_in(pert, nb * (size_t)cfg->T * fsz, c->p_stage, c->stream, a.pert));
+    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
     OutStage d, w;
     HIP_TRY(d.bind(d_out, c->d_stage, nb));
     HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
     a.d_out = (int8_t *)d.dev;
     a.frame_res = (int4 *)w.dev;
-    ldpc_counts before;
-    rc = read_counts(c, &before, 0);
-    if (rc) return rc;
-    rc = gdbf_run(c, a, f64);
-    if (rc) return rc;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(gdbf_run(c, a, f64));
     HIP_TRY(d.fetch(c->stream));
     HIP_TRY(w.fetch(c->stream));
-    return counts_delta(c, before, counts);
+    return c->counts_since(before, counts);
 }
 
 static int gdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_cfg *cfg, uint64_t seed,
                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    int rc = gdbf_check_cfg(cfg);
-    if (rc) return rc;
+    RC_TRY(gdbf_check_cfg(cfg));
     if (batch <= 0 || batch > c->max_batch)
         return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
     if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
     if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
-    HIP_TRY(hipSetDevice(c->device));
+    RC_TRY(c->enter());
     ldpc::GdbfArgs a;
     gdbf_fill(a, c, cfg, batch);
     a.src = ldpc::SRC_PHILOX;
@@ -1224,22 +930,19 @@ int ldpc_gdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_c
                         ldpc_counts *accum)
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    HIP_TRY(hipSetDevice(c->device));
-    ldpc_counts before;
-    int rc = read_counts(c, &before, 0);
-    if (rc) return rc;
+    RC_TRY(c->enter());
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
     OutStage w;   // batch is checked by gdbf_sim_impl
     HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
-    rc = gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev);
-    if (rc) return rc;
+    RC_TRY(gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev));
     HIP_TRY(w.fetch(c->stream));
-    return counts_delta(c, before, accum);
+    return c->counts_since(before, accum);
 }
 
 int ldpc_gdbf_kernel_info(ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, char *name, int name_len, int *lds_bytes)
 {
-    int rc = gdbf_check_cfg(cfg);
-    if (rc) return rc;
+    RC_TRY(gdbf_check_cfg(cfg));
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
     const ldpc::GdbfChoice ch = ldpc::gdbf_choose(c->dg, cfg->precision == LDPC_F64, cfg->flags, c->g->maxdv, c->g->maxdc);

@@ -11,7 +11,7 @@
 // in the translation unit's g_ldpc_check record, and the index is replaced by 0 so
 // that it never becomes an out-of-bounds access (no trap, no fault); the ABI call
 // that ran the launch then fails with LDPC_ERR_DEVICE naming the site
-// (api.cpp check_device_indices).
+// (host_rt.h LDPC_CHECK_AFTER_LAUNCH in CtxCore::end_launch, api.cpp check_collect).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>

@@ -1,0 +1,280 @@
+// host_rt.h -- the host runtime under both C ABIs (api.cpp: binary codes; nb_api.cpp:
+// GF(q)): error reporting, device buffers, host-or-device staging of inputs and
+// outputs, blob uploads, and CtxCore, the part of a context the two share (device,
+// streams, launch events, options, counters). Header only: both files include it.
+#pragma once
+#include "ldpc_hip.h"
+#include "blob.h"
+#include "check.h"
+#include "options.h"
+
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <initializer_list>
+#include <string>
+
+namespace ldpc {
+
+// ldpc_last_error() of api.cpp.
+int set_last_error(int code, const std::string &msg);
+
+inline int set_err(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+inline int set_err(int code, const char *fmt, ...)
+{
+    char buf[1024];
+    va_list ap;
+    va_start(ap, fmt);
+    std::vsnprintf(buf, sizeof buf, fmt, ap);
+    va_end(ap);
+    return set_last_error(code, buf);
+}
+
+// In a function that returns an ABI status: a failed HIP call ends it with LDPC_ERR_DEVICE ...
+#define HIP_TRY(expr)                                                                                 \
+    do {                                                                                              \
+        hipError_t e_ = (expr);                                                                       \
+        if (e_ != hipSuccess) {                                                                       \
+            (void)hipGetLastError();                                                                  \
+            return ::ldpc::set_err(LDPC_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), \
+                                   __FILE__, __LINE__);                                               \
+        }                                                                                             \
+    } while (0)
+// ... and a failed step (its last error is set) with that step's status.
+#define RC_TRY(expr)                        \
+    do {                                    \
+        if (const int rc_ = (expr)) return rc_; \
+    } while (0)
+
+#ifdef LDPC_CHECK
+// checked builds: every launch is synchronised and its indices' record read (check.h)
+#define LDPC_CHECK_AFTER_LAUNCH(stream)                                                                       \
+    do {                                                                                                      \
+        char m_[192];                                                                                         \
+        const long n_ = ::ldpc::check_collect((stream), m_, sizeof m_);                                       \
+        if (n_ < 0) return ::ldpc::set_err(LDPC_ERR_DEVICE, "check_collect: %s", hipGetErrorString((hipError_t)-n_)); \
+        if (n_ > 0) return ::ldpc::set_err(LDPC_ERR_DEVICE, "%s; %ld violations", m_, n_);                    \
+    } while (0)
+#else
+#define LDPC_CHECK_AFTER_LAUNCH(stream) ((void)0)
+#endif
+
+// A grow-only device allocation.
+struct DevBuf {
+    void *p = nullptr;
+    size_t n = 0;
+    hipError_t ensure(size_t bytes)
+    {
+        if (bytes <= n) return hipSuccess;
+        release();
+        hipError_t e = hipMalloc(&p, bytes);
+        if (e == hipSuccess) n = bytes;
+        return e;
+    }
+    void release()
+    {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+inline bool is_device_ptr(const void *p)
+{
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
+}
+
+// An output the caller may hold on the host or on the device: the kernel writes dev (the
+// caller's own pointer, or the staging buffer when that is host memory; null: not wanted),
+// and fetch() copies a staged output back once the launch is queued.
+struct OutStage {
+    void *user = nullptr, *dev = nullptr;
+    size_t bytes = 0;
+    hipError_t bind(void *out, DevBuf &stage, size_t n)
+    {
+        user = dev = out;
+        bytes = n;
+        if (!out || is_device_ptr(out)) return hipSuccess;
+        const hipError_t e = stage.ensure(n);
+        dev = stage.p;
+        return e;
+    }
+    hipError_t fetch(hipStream_t s) const
+    {
+        return dev == user ? hipSuccess : hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s);
+    }
+};
+
+// Its input counterpart: dev is where the kernel reads the n bytes of `in` -- `in` itself
+// when that is device memory (or null), else the staging buffer, with the copy queued on s.
+template <class T> hipError_t stage_in(const T *in, size_t n, DevBuf &stage, hipStream_t s, const T *&dev)
+{
+    dev = in;
+    if (!in || is_device_ptr(in)) return hipSuccess;
+    const hipError_t e = stage.ensure(n);
+    if (e != hipSuccess) return e;
+    dev = (const T *)stage.p;
+    return hipMemcpyAsync(stage.p, in, n, hipMemcpyHostToDevice, s);
+}
+
+// The device copy of a blob: one allocation, one copy; sections are at buf.p + their offsets.
+inline hipError_t upload(const Blob &b, DevBuf &buf)
+{
+    const hipError_t e = buf.ensure(b.size());
+    return e != hipSuccess || !b.size() ? e : hipMemcpy(buf.p, b.data(), b.size(), hipMemcpyHostToDevice);
+}
+
+// The device counters of a context are 8 words: bit, frame, uncoded bit errors, frames,
+// iterations, syndrome failures (the fields ldpc_counts and ldpc_nb_counts share, in
+// order), symbol errors (GF(q) only) and the codeword ticket of the GDBF / EMS launches
+// (which each launch clears itself). Counts are reported as differences of two reads.
+constexpr int kCountWords = 8;
+template <class Counts>
+void add_shared_counts(Counts *acc, const unsigned long long *after, const unsigned long long *before)
+{
+    int64_t *const f[6] = {&acc->bit_err, &acc->frame_err, &acc->uncoded_bit_err,
+                           &acc->frames,  &acc->iters,     &acc->syndrome_fail};
+    for (int i = 0; i < 6; ++i) *f[i] += (int64_t)(after[i] - before[i]);
+}
+inline void add_counts(ldpc_counts *acc, const unsigned long long *after, const unsigned long long *before)
+{
+    add_shared_counts(acc, after, before);
+}
+inline void add_counts(ldpc_nb_counts *acc, const unsigned long long *after, const unsigned long long *before)
+{
+    add_shared_counts(acc, after, before);
+    acc->symbol_err += (int64_t)(after[6] - before[6]);
+}
+
+// What ldpc_ctx and ldpc_nb_ctx share. Every ABI function that touches the device calls
+// enter() first; a launch is bracketed by begin_launch() / end_launch().
+struct CtxCore {
+    int device = 0, max_batch = 0, num_cus = 0;
+    hipStream_t own = nullptr, stream = nullptr;   // the context's own stream; the one launches go to
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;       // around the last launch (last_kernel_ms)
+    hipEvent_t handoff = nullptr;                  // orders the launches of a context across set_stream
+    bool timed = false;
+    Options opts;                                  // kernel-selection options (set_option), tests and A/B only
+    DevBuf counts;
+
+    int init(int dev, int batch)
+    {
+        device = dev;
+        max_batch = batch;
+        RC_TRY(enter());
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, device));
+        num_cus = prop.multiProcessorCount;
+        HIP_TRY(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
+        stream = own;
+        HIP_TRY(hipEventCreate(&ev0));
+        HIP_TRY(hipEventCreate(&ev1));
+        HIP_TRY(counts.ensure(kCountWords * sizeof(unsigned long long)));
+        HIP_TRY(hipMemset(counts.p, 0, counts.n));
+        return LDPC_OK;
+    }
+    // Waits for the current stream, then frees `bufs` and everything init() made. Any
+    // partly initialised context is fine: this is also the failure path of the *_create calls.
+    void destroy(std::initializer_list<DevBuf *> bufs)
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        for (DevBuf *b : bufs) b->release();
+        counts.release();
+        for (hipEvent_t ev : {ev0, ev1, handoff})
+            if (ev) (void)hipEventDestroy(ev);
+        if (own) (void)hipStreamDestroy(own);
+    }
+    int enter()
+    {
+        HIP_TRY(hipSetDevice(device));
+        return LDPC_OK;
+    }
+    int set_stream(void *s)
+    {
+        const hipStream_t ns = s ? (hipStream_t)s : own;
+        if (ns != stream) {
+            // The launches of one context share its counters (the GDBF / EMS codeword ticket
+            // included), staging and re-decode buffers: the new stream starts after everything
+            // already queued on the old one, so launches never overlap across a stream change.
+            RC_TRY(enter());
+            if (!handoff) HIP_TRY(hipEventCreateWithFlags(&handoff, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(handoff, stream));
+            HIP_TRY(hipStreamWaitEvent(ns, handoff, 0));
+        }
+        stream = ns;
+        return LDPC_OK;
+    }
+    int begin_launch()
+    {
+        HIP_TRY(hipEventRecord(ev0, stream));
+        return LDPC_OK;
+    }
+    int end_launch()
+    {
+        HIP_TRY(hipEventRecord(ev1, stream));
+        timed = true;
+        LDPC_CHECK_AFTER_LAUNCH(stream);
+        return LDPC_OK;
+    }
+    int last_kernel_ms(float *ms)
+    {
+        if (!ms) return set_err(LDPC_ERR_INVALID, "null argument");
+        if (!timed) return set_err(LDPC_ERR_INVALID, "no kernel launched yet");
+        RC_TRY(enter());
+        HIP_TRY(hipEventSynchronize(ev1));
+        HIP_TRY(hipEventElapsedTime(ms, ev0, ev1));
+        return LDPC_OK;
+    }
+    // The EMS options belong to the GF(q) context and only there (options.h).
+    int set_option(int option, int value, bool ems)
+    {
+        const bool ok = option_value_ok(option, value);
+        if (ems) {
+            if (!option_is_ems(option)) return set_err(LDPC_ERR_INVALID, "option %d is not an EMS option", option);
+            if (!ok) return set_err(LDPC_ERR_INVALID, "option %d: value %d out of range", option, value);
+        } else {
+            if (!ok) return set_err(LDPC_ERR_INVALID, "option %d: unknown, or value %d out of range", option, value);
+            if (option_is_ems(option))
+                return set_err(LDPC_ERR_INVALID, "option %d is an EMS option (ldpc_nb_ctx_set_option)", option);
+        }
+        opts.v[option] = value;
+        return LDPC_OK;
+    }
+    // The counters once everything queued on the stream has run (waits for it).
+    int read_counts_raw(unsigned long long v[kCountWords])
+    {
+        HIP_TRY(hipMemcpyAsync(v, counts.p, kCountWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return LDPC_OK;
+    }
+    template <class Counts> int read_counts(Counts *out, int reset)
+    {
+        unsigned long long v[kCountWords];
+        const unsigned long long zero[kCountWords] = {};
+        RC_TRY(read_counts_raw(v));
+        if (out) {
+            *out = Counts{};
+            add_counts(out, v, zero);
+        }
+        if (reset) HIP_TRY(hipMemsetAsync(counts.p, 0, counts.n, stream));   // stream-ordered: no wait
+        return LDPC_OK;
+    }
+    // acc += what the launches since the read `before` counted (acc may be null; waits for the stream).
+    template <class Counts> int counts_since(const unsigned long long *before, Counts *acc)
+    {
+        unsigned long long after[kCountWords];
+        RC_TRY(read_counts_raw(after));
+        if (acc) add_counts(acc, after, before);
+        return LDPC_OK;
+    }
+};
+
+}  // namespace ldpc

@@ -51,7 +51,4 @@ NbChoice nb_choose(const NbDevGraph &g, int maxdc);
 hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, void *scratch, int slots,
                      int num_cus, hipStream_t s);
 
-// ldpc_last_error() of api.cpp.
-int set_last_error(int code, const std::string &msg);
-
 }  // namespace ldpc

@@ -7,11 +7,14 @@
 // built with -fsanitize=address,undefined and run over every code given on the
 // command line, plus malformed inputs. Built and run by `make asan`
 // (tests/test_host_asan.py); any sanitizer report aborts with a non-zero status.
+// Also the sectioned-blob builder of the device uploads (blob.h) against the layouts
+// the contexts have always used.
 //   usage: host_asan [binary.alist ...] [--nb nb.alist ...] [--cw codeword-file ...] [--tmp DIR]
 #include "graph.h"
 #include "nb_graph.h"
 #include "nb_layout.h"
 #include "cli_common.h"
+#include "blob.h"
 #include "ldpc_hip.h"
 extern "C" {
 #include "ldpc_oracle.h"
@@ -19,6 +22,7 @@ extern "C" {
 
 #include <sstream>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -249,6 +253,41 @@ static void cli_inputs(const std::string &dir)
     CHECK(dv == 0 && dc == 0, "alist_header of a missing file");
 }
 
+// The device layouts of the contexts (host_rt.h upload): section offsets and total size
+// as the contexts' al() (256-byte sections: graph, row / flood / layered schedules) and
+// put() (16-byte sections: the GF(q) graph) arithmetic always gave them, written out by
+// hand: al(n) = (n + 255) & ~255 summed in order; put: off = (off + n + 15) & ~15.
+static void blob_layout()
+{
+    struct Case {
+        size_t align, bytes[5], off[5], total;
+    };
+    const Case cases[] = {{256, {0, 1, 255, 256, 257}, {0, 0, 256, 512, 768}, 1280},
+                          {16, {0, 1, 15, 16, 17}, {0, 0, 16, 32, 48}, 80}};
+    for (const Case &c : cases) {
+        ldpc::Blob b(c.align);
+        std::vector<std::vector<unsigned char>> src;
+        for (int i = 0; i < 5; ++i) {
+            src.emplace_back(c.bytes[i], (unsigned char)(0xA0 + i));   // exact-size sources: ASan sees any over-read
+            const size_t off = b.add(src[i].data(), src[i].size());
+            CHECK(off == c.off[i], "Blob(%zu): section %d of %zu bytes at %zu, want %zu", c.align, i, c.bytes[i], off,
+                  c.off[i]);
+        }
+        CHECK(b.size() == c.total, "Blob(%zu): %zu bytes, want %zu", c.align, b.size(), c.total);
+        std::vector<unsigned char> want(c.total, 0);   // sections read back, padding is zero
+        for (int i = 0; i < 5; ++i) std::fill_n(want.begin() + c.off[i], c.bytes[i], (unsigned char)(0xA0 + i));
+        CHECK(b.size() == want.size() && std::equal(want.begin(), want.end(), b.data()), "Blob(%zu): bytes differ", c.align);
+    }
+    // the graph blob's col_refs section: E entries copied, room for E + 1 (E = 64: 260 -> 512 bytes;
+    // E = 0: nothing copied, 256 bytes), and a vector section after it
+    const std::vector<uint32_t> refs(64, 0x01020304u), none;
+    ldpc::Blob g(256);
+    CHECK(g.add(refs.data(), 4 * refs.size(), 4 * (refs.size() + 1)) == 0 && g.size() == 512, "Blob: room of E + 1 entries");
+    CHECK(g.add(none.data(), 0, 4) == 512 && g.size() == 768, "Blob: empty section with room");
+    CHECK(g.add(refs) == 768 && g.size() == 1024 && g.data()[767] == 0 && g.data()[768] == 4, "Blob: vector section");
+    std::printf("blob layout: ok\n");
+}
+
 int main(int argc, char **argv)
 {
     std::string tmp = "/tmp";
@@ -266,6 +305,7 @@ int main(int argc, char **argv)
     for (const char *p : cw) one_codeword_file(p, 1008);
     nb_malformed(tmp);
     cli_inputs(tmp);
+    blob_layout();
     // malformed graphs: rejected with a message, never a crash
     {
         const int nn[2] = {1, 1}, nm[1] = {3};

@@ -54,6 +54,7 @@ def test_graph_compiler_and_oracle_clean_under_asan_ubsan():
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
     assert "ok (0 failures)" in p.stdout
     assert "runtime error" not in p.stderr and "AddressSanitizer" not in p.stderr
+    assert "blob layout: ok" in p.stdout   # blob.h: the device layouts' section offsets, literal numbers
     # the GF(16) code loads, with swizzles whose XOR over every check is 0 (checked inside)
     assert "gf16_N1000_dv2_dc4.alist: NB N=1000 M=500 q=16 E=2000" in p.stdout
     assert "q4.sp.9000.6000.4500.1.alist: NB N=9000 M=6000 q=4" in p.stdout
