@@ -14,10 +14,10 @@ CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 LIB       = $(LIBDIR)/libldpc_hip.so
 # the min-sum kernel families that `make variant` rebuilds (one translation unit each)
 MINSUM    = kernels rows flood layered
-OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf bp nb nb_api nb_graph api graph)
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf ddbmp bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
-            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF
+            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP
 
 # VFLAGS (-D switches of the A/B experiments, some of them wrong-result by design) belong
 # to the *variant targets, which build into ab/ with -DLDPC_AB_BUILD; the product refuses
@@ -62,6 +62,7 @@ FLAGS_layered   = $(KERNFLAGS) $(NOSLP)
 FLAGS_rows_fast = $(KERNFLAGS)
 FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
 FLAGS_gdbf      = $(NOSLP)
+FLAGS_ddbmp     = $(NOSLP)
 FLAGS_nb        = $(NOSLP)
 HDRS      = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h
 $(LIBDIR)/obj/%.o: $(CSRC)/%.hip $(HDRS) | $(LIBDIR)/obj
@@ -87,6 +88,10 @@ $(BINDIR)/decodeOffsetMinSum: $(CLI_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 
 $(BINDIR)/decodeBP: $(CLI_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D beliefPropagation -o $@ $< $(CLI_LINK)
+
+# DD-BMP (C_implementations/Makefile: decodeDDBMP), the quantiser always on.
+$(BINDIR)/decodeDDBMP: $(CLI_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
+	g++ $(CXXFLAGS) -D ddbmp -o $@ $< $(CLI_LINK)
 
 # GDBF / NGDBF front-ends: the -D switches of C_implementations/Makefile:33-53.
 GDBF_SRC = $(CSRC)/cli_gdbf.cpp

@@ -68,8 +68,12 @@ typedef enum {
  * src/decodeMinSum.cpp:494-499), OMS = -D offsetMS (:503-515), BP = the
  * tanh rule of src/decodeBP.cpp (:353-409) with its LLR front-end
  * yq = 4*y/n0 clipped to +-max_llr (:184-197; quantize/saturate ignored,
- * flooding only). */
-typedef enum { LDPC_MS = 0, LDPC_NMS = 1, LDPC_OMS = 2, LDPC_BP = 3 } ldpc_variant;
+ * flooding only). DDBMP = differential decoding with binary message passing
+ * (src/decodeDDBMP.cpp: one-bit messages, one memory per edge, :350-423) with
+ * the min-sum front-end (quantize / saturate / ymax / qbits; its CLI sets
+ * quantize); alpha, delta, n0 and max_llr are ignored; flooding only; T is a
+ * maximum, the decoder stops when H*d = 0 (:203-204). */
+typedef enum { LDPC_MS = 0, LDPC_NMS = 1, LDPC_OMS = 2, LDPC_BP = 3, LDPC_DDBMP = 4 } ldpc_variant;
 
 /* Message arithmetic. F64 is the reference's own precision and reproduces
  * its decisions bit-for-bit for identical y; F32 is the throughput path. */
@@ -102,13 +106,17 @@ typedef struct {
     int32_t bit_err;          /* newErrors of :270 (0 = frame decoded)  */
     int32_t uncoded_bit_err;  /* hard-decision errors before decoding    */
     int32_t syndrome_fail;    /* 1 if H*d != 0                          */
-    int32_t iters;            /* GDBF: iterations run (`it`, decodeGDBF.cpp:399); min-sum: 0 */
+    int32_t iters;            /* GDBF: iterations run (`it`, decodeGDBF.cpp:399); DD-BMP:
+                               * `it` of decodeDDBMP.cpp:230 (a frame that stops inside
+                               * iteration index it counts it, one that never stops T);
+                               * min-sum, BP: 0 */
 } ldpc_frame_result;
 
 typedef struct {
     int32_t variant;    /* ldpc_variant                                     */
     int32_t precision;  /* ldpc_precision                                   */
-    int32_t T;          /* iterations (num_iterations), fixed, no early stop */
+    int32_t T;          /* iterations (num_iterations): fixed, no early stop;
+                         * DD-BMP: the maximum (early stop)                   */
     int32_t quantize;   /* -D quantizeSamples: quantize(y, ymax, 2^qbits)   */
     int32_t saturate;   /* -D saturateSamples: clip at +-ymax               */
     int32_t qbits;      /* Q                                                */
@@ -227,7 +235,8 @@ int  ldpc_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_decoder_
  * the launch stream around it. Synchronises that stream. */
 int  ldpc_ctx_last_kernel_ms(ldpc_ctx *ctx, float *ms);
 /* Kernel chosen for a cfg ("rows_pp", "rows_fast", "rows", "lds", "flood",
- * "global", "layered_*", "bp_*") and its per-codeword LDS bytes. */
+ * "global", "layered_*", "bp_*", "ddbmp_rows" / "ddbmp_lds" / "ddbmp_global")
+ * and its per-codeword LDS bytes. */
 int  ldpc_ctx_kernel_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, char *name, int name_len,
                           int *lds_bytes, int *blocks_per_cu);
 /* Codewords of the last min-sum launch that the fast row kernel (fp64,
@@ -242,7 +251,7 @@ int  ldpc_ctx_redo_count(ldpc_ctx *ctx, int64_t *n);
  * e_pad, codewords per block, LDS bytes per block, blocks per CU, the low row
  * degree of rows_pp's degree-aware slots (0: every slot runs the padded degree),
  * check-node edge slots issued per codeword-iteration} (ABI 10: 10 entries).
- * LDPC_ERR_UNSUPPORTED when another kernel decodes cfg. Host-only, no device
+ * LDPC_ERR_UNSUPPORTED when another kernel decodes cfg (always for BP and DD-BMP). Host-only, no device
  * call. No reference counterpart (diagnostic of decodeMinSum.cpp:247-263's
  * replacement). */
 int  ldpc_ctx_row_sched_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t *info);
@@ -276,9 +285,10 @@ typedef enum {
     LDPC_OPT_BP_KERNEL = 18,       /* belief propagation: 0 bp_rows when the code fits, 1 the generic kernel  */
     LDPC_OPT_GDBF_KERNEL = 19,     /* GDBF: 0 gdbf_rows when the code and flags fit, 1 the generic kernel     */
     LDPC_OPT_EMS_THREADS = 20,     /* EMS (nb context), row degree 4: 0 = 1024 threads, 512                   */
-    LDPC_OPT_EMS_SWIZZLE = 21      /* EMS (nb context): 0 swizzled message slots, 1 the plain layout          */
+    LDPC_OPT_EMS_SWIZZLE = 21,     /* EMS (nb context): 0 swizzled message slots, 1 the plain layout          */
+    LDPC_OPT_DDBMP_KERNEL = 22     /* DD-BMP: 0 ddbmp_rows when the code fits, 1 the generic kernel           */
 } ldpc_option;
-#define LDPC_OPT_COUNT 22
+#define LDPC_OPT_COUNT 23
 /* LDPC_ERR_INVALID for an unknown option, a value outside its range, or an
  * EMS option (LDPC_OPT_EMS_*: the nb context's, ldpc_nb_ctx_set_option). */
 int  ldpc_ctx_set_option(ldpc_ctx *ctx, int option, int value);

@@ -8,6 +8,7 @@
 #include "ldpc_hip.h"
 #include "gdbf.h"
 #include "bp.h"
+#include "ddbmp.h"
 #include "nb.h"
 
 #include <hip/hip_runtime.h>
@@ -38,7 +39,7 @@ static const char *check_site_name(unsigned s)
         "rows_pp app write", "rows_fast gather (app entry)", "rows_fast scatter (c2v slot)",
         "rows_fast bit read (c2v slot)", "rows_fast app write", "flood/layered bit position",
         "flood c2v / eref slot", "flood packed-state row", "gdbf_rows bit", "gdbf_rows check term slot",
-        "EMS message slot", "bp_rows bit", "bp_rows message slot"};
+        "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -46,7 +47,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
-                                              check_take_gdbf, check_take_nb, check_take_bp};
+                                              check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -108,6 +109,7 @@ bool option_value_ok(int option, int v)
     case LDPC_OPT_FLOOD_MSG:
     case LDPC_OPT_BP_KERNEL:
     case LDPC_OPT_GDBF_KERNEL:
+    case LDPC_OPT_DDBMP_KERNEL:
     case LDPC_OPT_EMS_SWIZZLE: return v == 0 || v == 1;
     case LDPC_OPT_KERNEL: return v >= 0 && v <= 3;
     case LDPC_OPT_FLOOD_SPS_CHECK:
@@ -440,13 +442,15 @@ int ldpc_ctx_get_option(const ldpc_ctx *c, int option, int *value)
 static int check_cfg(const ldpc_ctx *c, const ldpc_decoder_cfg *cfg)
 {
     if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
-    if (cfg->variant < LDPC_MS || cfg->variant > LDPC_BP) return set_err(LDPC_ERR_INVALID, "bad variant %d", cfg->variant);
+    if (cfg->variant < LDPC_MS || cfg->variant > LDPC_DDBMP) return set_err(LDPC_ERR_INVALID, "bad variant %d", cfg->variant);
     if (cfg->variant == LDPC_BP) {
         if (cfg->schedule != LDPC_FLOODING) return set_err(LDPC_ERR_UNSUPPORTED, "BP is flooding only");
         if (c->g->maxdc > ldpc::kBpMaxDc)
             return set_err(LDPC_ERR_UNSUPPORTED, "BP supports row degree <= %d", ldpc::kBpMaxDc);
         if (cfg->max_llr < 0) return set_err(LDPC_ERR_INVALID, "max_llr must be >= 0");
     }
+    if (cfg->variant == LDPC_DDBMP && cfg->schedule == LDPC_LAYERED)
+        return set_err(LDPC_ERR_UNSUPPORTED, "DD-BMP is flooding only");
     if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
         return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
     if (cfg->T < 0) return set_err(LDPC_ERR_INVALID, "T must be >= 0");
@@ -518,11 +522,13 @@ static ldpc::LaunchPlan build_plan(const ldpc_ctx *c, const ldpc::DecodeArgs &a,
     enum { AUTO = 0, LDS = 1, FLOOD = 2, GLOBAL = 3 };   // values of LDPC_OPT_KERNEL
     const ldpc::OptScope os(c->opts);
     const ldpc::PlanInput in{c->dg, c->g->E, c->has_rs ? &c->rs : nullptr, c->has_rs_pp ? &c->rs_pp : nullptr,
-                             c->has_fs ? &c->fs : nullptr, c->has_ls ? &c->ls : nullptr, c->num_cus, a, f64};
+                             c->has_fs ? &c->fs : nullptr, c->has_ls ? &c->ls : nullptr, c->num_cus, a, f64, c->g->maxdv};
     const int force = c->opts.v[LDPC_OPT_KERNEL];
     ldpc::LaunchPlan p;
     if (a.variant == ldpc::VARIANT_BP) {
         ldpc::plan_bp(in, p);
+    } else if (a.variant == ldpc::VARIANT_DDBMP) {
+        ldpc::plan_ddbmp(in, p);
     } else if (schedule == LDPC_LAYERED) {
         ldpc::plan_layered(in, p);   // check_cfg: the context has the layered schedule
     } else {
@@ -571,6 +577,12 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
     case Kernel::bp_rows:
     case Kernel::bp_lds:
     case Kernel::bp_global: HIP_TRY(ldpc::launch_bp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->stream)); break;
+    case Kernel::ddbmp_rows:
+    case Kernel::ddbmp_lds:
+    case Kernel::ddbmp_global:   // the ticket: the 8th word of counts (host_rt.h), as the GDBF launches'
+        HIP_TRY(ldpc::launch_ddbmp(p, c->dg, a, f64, c->g->E, c->gscratch.p,
+                                   reinterpret_cast<unsigned *>((unsigned long long *)c->counts.p + 7), c->stream));
+        break;
     }
     // the exact re-decode of any codeword whose fast-path premise failed
     if (p.redo) HIP_TRY(ldpc::launch_redo(c->dg, a, f64, (const unsigned *)c->redo.p, c->stream, c->num_cus));

@@ -36,6 +36,8 @@ enum CheckSite : unsigned {
     CHK_EMS_SLOT,          // EMS: message slot of a check / symbol edge    (< Ep)
     CHK_BP_COL,            // bp_rows: bit a check row gathers              (< N + 1)
     CHK_BP_MSG,            // bp_rows: message slot                         (< E + 1)
+    CHK_DDBMP_EDGE,        // ddbmp: flag byte of an edge in its row's slot  (< rows * stride)
+    CHK_DDBMP_CHECK,       // ddbmp: parity byte of a check                 (< rows)
     CHK_SITES
 };
 
@@ -96,6 +98,7 @@ hipError_t check_take_layered(CheckRec *out);
 hipError_t check_take_gdbf(CheckRec *out);
 hipError_t check_take_nb(CheckRec *out);
 hipError_t check_take_bp(CheckRec *out);
+hipError_t check_take_ddbmp(CheckRec *out);
 #endif
 
 }  // namespace ldpc

@@ -4,7 +4,10 @@
 // (C_implementations/src/decodeMinSum.cpp:72-334) and, built with
 // -D beliefPropagation, for decodeBP (src/decodeBP.cpp:58-277: the tanh rule,
 // LLR front-end 4y/N0, stop rule 200 errors / 20|10|5 word errors, its own
-// parameter block and log line): the same positional CLI
+// parameter block and log line) and, built with -D ddbmp, for decodeDDBMP
+// (src/decodeDDBMP.cpp:55-270: alist R SNR T Ymax Q logfilename [codeword filename],
+// the quantiser always on, early stop, log line SNR BER avgIt FER T Ymax Q alist):
+// the same positional CLI
 //   decodeMinSum alist R SNR T [Ymax] [Q] [alpha] [delta] logfilename [codewordfile]
 // with the variant fixed at compile time by the same -D macros
 // (quantizeSamples, saturateSamples, normalizedMS, offsetMS; Makefile:58-65),
@@ -96,6 +99,9 @@ int main(int argc, char *argv[])
 #ifdef beliefPropagation
     args = {"alist", "R", "SNR", "T", "logfilename", "[codeword filename]"};   // decodeBP.cpp:60-67
 #endif
+#ifdef ddbmp
+    args = {"alist", "R", "SNR", "T", "Ymax", "Q", "logfilename", "[codeword filename]"};   // decodeDDBMP.cpp:57-65
+#endif
     if ((size_t)argc != args.size() && (size_t)argc != args.size() + 1) {   // :95-102
         cout << "Usage: " << argv[0];
         for (const auto &a : args) cout << " " << a;
@@ -122,6 +128,16 @@ int main(int argc, char *argv[])
     const int T = std::atoi(argv[idx++]);
     cout << " T = \t" << T << endl;
     cfg.T = T;
+#ifdef ddbmp
+    cfg.variant = LDPC_DDBMP;   // decodeDDBMP.cpp:87-90 ("Q" has no leading space there)
+    const double Ymax = std::atof(argv[idx++]);
+    cout << " Ymax = \t" << Ymax << endl;
+    const int Q = std::atoi(argv[idx++]);
+    cout << "Q = \t" << Q << endl;
+    cfg.quantize = 1;
+    cfg.ymax = Ymax;
+    cfg.qbits = Q;
+#endif
 #ifdef saturateSamples
     const double Ymax = std::atof(argv[idx++]);
     cout << "Applying sample clipping with Ymax = +/-" << Ymax << endl;
@@ -167,7 +183,12 @@ int main(int argc, char *argv[])
     const double sigma = std::sqrt(N0 / 2.0);
     int dv = 0, dc = 0;
     alist_header(argv[1], dv, dc);
-    cout << "Simulating Min-Sum decoding on code with N=" << N << ", M=" << M << ", R=" << R << ", dv=" << dv
+#ifdef ddbmp
+    const char *const algorithm = "DD-BMP";   // decodeDDBMP.cpp:113
+#else
+    const char *const algorithm = "Min-Sum";
+#endif
+    cout << "Simulating " << algorithm << " decoding on code with N=" << N << ", M=" << M << ", R=" << R << ", dv=" << dv
          << ", dc=" << dc << endl;
 #ifdef beliefPropagation
     cout << "\nParameters are:\n\tSNR\t" << SNR << endl;   // decodeBP.cpp:114
@@ -269,7 +290,11 @@ int main(int argc, char *argv[])
             }
             totalWords++;   // :286-288
             totalBits += N;
+#ifdef ddbmp
+            totalIterations += res[f].iters;   // `it` of decodeDDBMP.cpp:230 (early stop)
+#else
             totalIterations += T;
+#endif
             if ((totalWords % 5) == 0) {   // :292-298
                 cout << "\nIncremental result: " << errors << " bit errs in " << totalWords
                      << " words, BER=" << (double)errors / totalBits
@@ -289,8 +314,11 @@ int main(int argc, char *argv[])
     const char tab = '\t';
     of << SNR << tab << (double)errors / totalBits << tab << (double)totalIterations / totalWords << tab
        << (double)wordErrors / totalWords << tab << T << tab;
-#if defined(saturateSamples) || defined(quantizeSamples)
+#if defined(saturateSamples) || defined(quantizeSamples) || defined(ddbmp)
     of << Ymax << tab;
+#endif
+#ifdef ddbmp
+    of << Q << tab;   // decodeDDBMP.cpp:257-261
 #endif
 #ifdef normalizedMS
     of << alpha << tab;

@@ -16,7 +16,7 @@ struct DevGraph {
 };
 
 enum { SRC_GIVEN = 0, SRC_PHILOX = 1 };
-enum { VARIANT_BP = 3 };   // ldpc_variant LDPC_BP
+enum { VARIANT_BP = 3, VARIANT_DDBMP = 4 };   // ldpc_variant LDPC_BP, LDPC_DDBMP
 
 struct DecodeArgs {
     int batch, T, variant, quantize, saturate;
@@ -36,7 +36,7 @@ struct DecodeArgs {
     double sigma;
     int8_t *d_out;                  // [batch][N] or null
     void *y_out;                    // SRC_PHILOX: channel samples [batch][N] F (pre front-end) or null
-    int4 *frame_res;                // [batch] {bit_err, uncoded, syndrome_fail, 0} or null
+    int4 *frame_res;                // [batch] {bit_err, uncoded, syndrome_fail, iterations (DD-BMP; else 0)} or null
     unsigned long long *counts;     // [6] accumulated
     unsigned long long *hist;       // [N] accumulated (weight w -> hist[w-1])
     unsigned long long *stamps;     // diagnostic builds (-DLDPC_STAMPS): [grid][4] cycle sums, else null
@@ -81,7 +81,8 @@ enum class Kernel {
     lds, global,                        // one workgroup per codeword (kernels.hip)
     flood_persistent, flood_phase,      // codes beyond LDS (flood.hip); both report "flood"
     layered_lds, layered_global,        // layered schedule (layered.hip)
-    bp_rows, bp_lds, bp_global          // belief propagation (bp.hip)
+    bp_rows, bp_lds, bp_global,         // belief propagation (bp.hip)
+    ddbmp_rows, ddbmp_lds, ddbmp_global // DD-BMP (ddbmp.hip)
 };
 
 // Everything one decode launch of the binary context needs, decided once (api.cpp
@@ -114,6 +115,7 @@ struct PlanInput {
     int num_cus;
     const DecodeArgs &a;            // after nms_setup; a.batch sizes the grid
     bool f64;
+    int maxdv = 0;                  // the code's largest column degree (plan_ddbmp)
 };
 
 // The (precision, sample source) template axes every kernel has: fn(type_tag<F>{}, src_tag<SRC>{}).

@@ -3,7 +3,7 @@
 // library's kernel choice through the C ABI, never through the environment.
 //
 // The launch helpers deep in the kernel files (kernels.hip, rows.hip, flood.hip, layered.hip, nb.hip, bp.hip,
-// gdbf.hip, rows_fast.hip) read them through opt(): each ABI entry point that
+// gdbf.hip, ddbmp.hip, rows_fast.hip) read them through opt(): each ABI entry point that
 // chooses or launches a kernel installs its context's options for the duration
 // of the call (OptScope). Outside such a call every option reads 0, the
 // library's own choice.

@@ -16,7 +16,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_PKG, "lib", "libldpc_hip.so")
 
 LDPC_OK = 0
-MS, NMS, OMS, BP = 0, 1, 2, 3
+MS, NMS, OMS, BP, DDBMP = 0, 1, 2, 3, 4
 F32, F64 = 0, 1
 FLOODING, LAYERED = 0, 1
 ABI_VERSION = 11
@@ -26,7 +26,7 @@ OPTIONS = {"rows64": 1, "rows32": 2, "pp_slots": 3, "kernel": 4, "flood_mode": 5
            "flood_sps_check": 7, "flood_sps_bit": 8, "flood_resident": 9, "flood_streams": 10, "flood_bpc": 11,
            "layered_bpc": 12, "layered_lds_pos": 13, "layered_rows64": 14, "layered_threads": 15,
            "rows_bpc": 16, "fast_bpc": 17, "bp_kernel": 18, "gdbf_kernel": 19, "ems_threads": 20,
-           "ems_swizzle": 21}
+           "ems_swizzle": 21, "ddbmp_kernel": 22}
 # options of the GF(q) EMS context only (ldpc_nb_ctx_set_option); the binary context refuses them
 EMS_OPTIONS = ("ems_threads", "ems_swizzle")
 # symbolic values of the kernel-choice options
@@ -34,6 +34,7 @@ OPTION_VALUES = {"rows64": {"pp": 0, "fast": 1, "rows": 2}, "rows32": {"pp": 0, 
                  "pp_slots": {"split": 0, "plain": 1}, "kernel": {"auto": 0, "lds": 1, "flood": 2, "global": 3},
                  "flood_mode": {"phase": 0, "persistent": 1}, "flood_msg": {"packed": 0, "c2v": 1},
                  "bp_kernel": {"rows": 0, "generic": 1}, "gdbf_kernel": {"rows": 0, "generic": 1},
+                 "ddbmp_kernel": {"rows": 0, "generic": 1},
                  "ems_swizzle": {"on": 0, "off": 1}}
 
 
@@ -130,8 +131,8 @@ class GdbfConfig:
 @dataclass
 class DecoderConfig:
     """Runtime form of the reference's compile-time decoder switches."""
-    variant: int = MS            # MS | NMS (-D normalizedMS) | OMS (-D offsetMS)
-    T: int = 10                  # iterations (fixed, no early termination)
+    variant: int = MS            # MS | NMS (-D normalizedMS) | OMS (-D offsetMS) | BP | DDBMP (decodeDDBMP.cpp)
+    T: int = 10                  # iterations (fixed, no early termination; DDBMP: the maximum)
     precision: int = F64         # F64 = the reference's double (default) | F32 throughput path (opt-in)
     alpha: float = 1.0           # NMS divisor
     delta: float = 0.0           # OMS offset

@@ -18,7 +18,10 @@ line for each point.
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 50 --variant bp
     # BASELINE config 5: GF(16) EMS on an NB alist (SystemC/NB-LDPC format), early stop
     python -m ldpcsimulation_amd.sweep codes/gf16_N1000_dv2_dc4.alist --ems --rate 0.5 --snr 1.5 2.0 -T 20
-Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (EMS: SNR BER avgIt FER T nm offset alist;
+    # DD-BMP (decodeDDBMP: the quantiser always on, early stop; the grid of its sweep script
+    # scripts/ddbmp_example_4000.2000.4.244.sh is one such call per (Ymax, Q))
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --variant ddbmp --ymax 1.0 --qbits 3
+Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
 BER over coded bits, 4 per GF(16) symbol).
 
 --checkpoint FILE appends each point's running totals after a round at most
@@ -36,7 +39,8 @@ import time
 
 from . import checkpoint, native, sim
 
-VARIANTS = {"ms": native.MS, "nms": native.NMS, "oms": native.OMS, "bp": native.BP}
+VARIANTS = {"ms": native.MS, "nms": native.NMS, "oms": native.OMS, "bp": native.BP,
+            "ddbmp": native.DDBMP}
 
 
 def parse(argv=None):
@@ -50,6 +54,8 @@ def parse(argv=None):
     p.add_argument("--delta", type=float, default=0.0)
     p.add_argument("--quantize", nargs=2, metavar=("YMAX", "Q"), help="-D quantizeSamples front-end")
     p.add_argument("--saturate", type=float, metavar="YMAX", help="-D saturateSamples front-end")
+    p.add_argument("--ymax", type=float, help="--variant ddbmp: Ymax of its quantiser (required)")
+    p.add_argument("--qbits", type=int, help="--variant ddbmp: Q of its quantiser (required)")
     p.add_argument("--precision", choices=["f32", "f64"], default="f64",
                    help="f64 = the reference's double (default); f32 = the fp32 kernels (opt-in)")
     p.add_argument("--schedule", choices=["flooding", "layered"], default="flooding",
@@ -82,13 +88,22 @@ def parse(argv=None):
     p.add_argument("--checkpoint-interval", type=float, default=10.0, metavar="S",
                    help="seconds between checkpoint records (0 = after every round); each record "
                         "all-reduces the point's error-weight histogram")
-    return p.parse_args(argv)
+    a = p.parse_args(argv)
+    if a.variant == "ddbmp":
+        if a.ymax is None or a.qbits is None:
+            p.error("--variant ddbmp needs --ymax and --qbits (decodeDDBMP: alist R SNR T Ymax Q log)")
+        if a.quantize or a.saturate is not None or a.schedule != "flooding" or a.ems:
+            p.error("--variant ddbmp takes its front-end from --ymax / --qbits and is flooding only")
+    elif a.ymax is not None or a.qbits is not None:
+        p.error("--ymax / --qbits belong to --variant ddbmp (min-sum: --quantize YMAX Q)")
+    return a
 
 
 def _checkpoint_config(a) -> dict:
     """Every setting that changes a point's result (not the batch or round sizes,
     the GPU count or the log options: exact_stop makes totals independent of them)."""
-    return {"alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
+    ddbmp = {"ymax": a.ymax, "qbits": a.qbits} if a.variant == "ddbmp" else {}
+    return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
             "snr": list(a.snr), "T": a.iterations, "variant": a.variant, "alpha": a.alpha, "delta": a.delta,
             "quantize": a.quantize, "saturate": a.saturate, "precision": a.precision, "schedule": a.schedule,
             "min_bit_errors": a.min_bit_errors, "min_frame_errors": a.min_frame_errors, "max_frames": a.max_frames,
@@ -167,6 +182,9 @@ def main(argv=None) -> int:
     elif a.saturate is not None:
         cfg.saturate, cfg.ymax = True, a.saturate
         extra.append(cfg.ymax)
+    if a.variant == "ddbmp":   # decodeDDBMP.cpp:255-264: ... T Ymax Q alist
+        cfg.quantize, cfg.ymax, cfg.qbits = True, a.ymax, a.qbits
+        extra += [cfg.ymax, cfg.qbits]
     if a.variant == "nms":
         extra.append(a.alpha)
     elif a.variant == "oms":
@@ -193,6 +211,7 @@ def main(argv=None) -> int:
         t0 = time.perf_counter()
         res = sim.simulate_point(run_batch, g.N, a.iterations, snr, a.batch, a.min_bit_errors,
                                  min_fe, a.max_frames, device=device, launcher=launcher, first_round=a.first_round,
+                                 iters_in_frames=a.variant == "ddbmp",   # early stop: frames report their `it`
                                  resume=resume, on_round=on_round,
                                  on_round_interval=a.checkpoint_interval)
         dt = time.perf_counter() - t0
@@ -200,6 +219,7 @@ def main(argv=None) -> int:
         ran = c["frames"] - (int(resume.acc[3]) if resume else 0)   # frames counted by this run
         return res, res.log_line(a.alist, extra), {
             "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, "seconds": dt,
+            **({"avg_iters": res.avg_iters} if a.variant == "ddbmp" else {}),
             "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None,
             "n_gpus": world, "wilson95": sim.wilson_interval(c["frame_err"], c["frames"]),
             "precision": a.precision, "schedule": a.schedule, "variant": a.variant,

@@ -32,7 +32,8 @@ the counters show busiest, and the other resources' fractions beside it:
 Which of these binds is a reading of the counters, not a proof: a kernel whose
 largest fraction is well below 1 is latency-bound, and the line says so.
 Reference paths: src/decodeMinSum.cpp:247-263 (configs 1-3), src/decodeGDBF.cpp:517-621
-(config 4), SystemC/NB-LDPC/inc/nodes.h:195-293 (config 5), src/decodeBP.cpp:353-409.
+(config 4), SystemC/NB-LDPC/inc/nodes.h:195-293 (config 5), src/decodeBP.cpp:353-409,
+src/decodeDDBMP.cpp:350-423 (the ddbmp_* lines).
 """
 import argparse
 import csv
@@ -78,6 +79,15 @@ CONFIGS = {
                           batch=16384, snr=1.5, what="BP (tanh rule) on 802.11n N=1944, T=50, fp64"),
     "bp_80211n_f32": dict(kind="minsum", code="80211n_1944_r12.alist", variant="bp", prec="f32", T=50,
                           batch=16384, snr=1.5, what="BP (tanh rule) on 802.11n N=1944, T=50, fp32"),
+    # DD-BMP (src/decodeDDBMP.cpp:350-423), Ymax 1.0, Q 3, at an Eb/N0 where most frames stop early
+    "ddbmp_80211n_f32": dict(kind="minsum", code="80211n_1944_r12.alist", variant="ddbmp", prec="f32", T=100,
+                             batch=65536, snr=5.0, what="DD-BMP on 802.11n N=1944, T<=100, Ymax 1.0, Q 3, fp32"),
+    "ddbmp_80211n_f64": dict(kind="minsum", code="80211n_1944_r12.alist", variant="ddbmp", prec="f64", T=100,
+                             batch=65536, snr=5.0, what="DD-BMP on 802.11n N=1944, T<=100, Ymax 1.0, Q 3, fp64"),
+    "ddbmp_peg1008_f32": dict(kind="minsum", code="PEGReg504x1008.alist", variant="ddbmp", prec="f32", T=100,
+                              batch=65536, snr=4.0, what="DD-BMP on PEG 504x1008, T<=100, Ymax 1.0, Q 3, fp32"),
+    "ddbmp_peg1008_f64": dict(kind="minsum", code="PEGReg504x1008.alist", variant="ddbmp", prec="f64", T=100,
+                              batch=65536, snr=4.0, what="DD-BMP on PEG 504x1008, T<=100, Ymax 1.0, Q 3, fp64"),
 }
 
 PMC_PASSES = [
@@ -130,7 +140,8 @@ class Workload:
             self.kernel = self.ctx.gdbf_kernel_info(self.cfg)["kernel"]
         else:
             v = {"ms": dict(variant=native.MS), "nms": dict(variant=native.NMS, alpha=1.25),
-                 "bp": dict(variant=native.BP)}[c["variant"]]
+                 "bp": dict(variant=native.BP),
+                 "ddbmp": dict(variant=native.DDBMP, quantize=True, ymax=1.0, qbits=3)}[c["variant"]]
             sched = native.LAYERED if c.get("schedule") == "layered" else native.FLOODING
             self.cfg = native.DecoderConfig(T=c["T"], precision=prec, schedule=sched, **v)
             self.launch_fn = self.ctx.sim_launch
