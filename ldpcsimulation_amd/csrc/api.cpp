@@ -579,9 +579,8 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
     case Kernel::bp_global: HIP_TRY(ldpc::launch_bp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->stream)); break;
     case Kernel::ddbmp_rows:
     case Kernel::ddbmp_lds:
-    case Kernel::ddbmp_global:   // the ticket: the 8th word of counts (host_rt.h), as the GDBF launches'
-        HIP_TRY(ldpc::launch_ddbmp(p, c->dg, a, f64, c->g->E, c->gscratch.p,
-                                   reinterpret_cast<unsigned *>((unsigned long long *)c->counts.p + 7), c->stream));
+    case Kernel::ddbmp_global:
+        HIP_TRY(ldpc::launch_ddbmp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->ticket(), c->stream));
         break;
     }
     // the exact re-decode of any codeword whose fast-path premise failed
@@ -852,7 +851,7 @@ static void gdbf_fill(ldpc::GdbfArgs &a, ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, 
     a.qsigma = cfg->qsigma;
     a.counts = (unsigned long long *)c->counts.p;
     a.hist = (unsigned long long *)c->hist.p;
-    a.ticket = reinterpret_cast<unsigned *>((unsigned long long *)c->counts.p + 7);   // the 8th word of counts
+    a.ticket = c->ticket();
 }
 
 static int gdbf_run(ldpc_ctx *c, const ldpc::GdbfArgs &a, bool f64)

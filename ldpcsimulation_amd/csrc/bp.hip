@@ -15,7 +15,7 @@
 // to a few ulp, not bit for bit: parity is by tolerance and by FER (tests/test_bp.py).
 #include "bp.h"
 #include "bp_math.h"
-#include "device_common.h"
+#include "frame.h"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -51,37 +51,13 @@ __device__ __forceinline__ void bp_codeword(const DecodeArgs &a, const DevGraph 
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int N = g.N, M = g.M, dcs = g.dcs;
-    const uint64_t cw = a.first_cw + (uint64_t)b;
     const F n0 = (F)a.n0, maxllr = (F)a.max_llr;
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     // ---- channel + LLR front-end (:184-197) ----
     int unc = 0;
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
     for (int g4 = tid; g4 * 4 < N; g4 += nt) {
         F yv[4];
-        if (SRC == SRC_GIVEN) {
-            const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) yv[q] = (g4 * 4 + q < N) ? y[g4 * 4 + q] : F(1);
-        } else {
-            uint32_t u[4];
-            philox4x32_10((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-            const F sigma = (F)a.sigma;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int v = g4 * 4 + q;
-                yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-                if (v < N && a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv[q];
-            }
-        }
+        channel_group<F, SRC, false, true>(a, b, g4, N, cvec, a.y_out, yv);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int v = g4 * 4 + q;
@@ -161,17 +137,7 @@ __device__ __forceinline__ void bp_codeword(const DecodeArgs &a, const DevGraph 
     }
     int sums[3] = {w, unc, synd};
     block_sum_n_t0<3>(sums, red);
-    if (tid == 0) {
-        const int sf = sums[2] > 0;
-        atomicAdd(&a.counts[0], (unsigned long long)sums[0]);
-        atomicAdd(&a.counts[1], (unsigned long long)(sums[0] > 0));
-        atomicAdd(&a.counts[2], (unsigned long long)sums[1]);
-        atomicAdd(&a.counts[3], 1ull);
-        atomicAdd(&a.counts[4], (unsigned long long)a.T);
-        atomicAdd(&a.counts[5], (unsigned long long)sf);
-        if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-        if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, 0);
-    }
+    if (tid == 0) frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
     __syncthreads();
 }
 
@@ -304,16 +270,21 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
 #pragma unroll
         for (int q = 0; q < 3; ++q) red[q] = 0;   // block_sum_lds totals
     }
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
+    // frame.h reads the frame's fields from a copy: this kernel hands `a` itself to no function, and
+    // the fp64 Philox instance (128 VGPRs, 124 bytes spilled) spills 144-148 bytes once it does.
+    // For the same reason the y_out store sits in the sample loop in fp64 and after it in fp32
+    // (fp64 after: 132 bytes spilled; fp32 inside: 77 VGPRs instead of 79 at 1024 threads).
+    const struct {
+        const void *y;
+        const int8_t *c, *cw_table;
+        int cw_rows;
+        uint64_t seed, first_cw;
+        uint32_t stream_id;
+        double sigma;
+    } fa = {a.y, a.c, a.cw_table, a.cw_rows, a.seed, a.first_cw, a.stream_id, a.sigma};
 
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
-        const uint64_t cw = a.first_cw + (uint64_t)b;
-        const int8_t *cvec = nullptr;
-        if (SRC == SRC_GIVEN) {
-            if (a.c) cvec = a.c + (size_t)b * N;
-        } else if (a.cw_table) {
-            cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-        }
+        const int8_t *cvec = frame_codeword<SRC>(fa, b, N);
         // ---- channel + LLR front-end (:184-197), as bp_codeword ----
         int unc = 0;
         F yq[4];
@@ -321,24 +292,7 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
         for (int q = 0; q < 4; ++q) yq[q] = F(0);
         if (own) {
             F yv[4];
-            if (SRC == SRC_GIVEN) {
-                const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) yv[q] = (v0 + q < N) ? y[v0 + q] : F(1);
-            } else {
-                uint32_t u[4];
-                philox4x32_10<true>((uint32_t)tid, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-                F n[4];
-                box_muller(u[0], u[1], n[0], n[1]);
-                box_muller(u[2], u[3], n[2], n[3]);
-                const F sigma = (F)a.sigma;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int v = v0 + q;
-                    yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-                    if (v < N && a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv[q];
-                }
-            }
+            channel_group<F, SRC, true, sizeof(F) == 4>(fa, b, tid, N, cvec, a.y_out, yv);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int v = v0 + q;
@@ -443,17 +397,7 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
         }
         int sums[3] = {w, unc, synd};
         block_sum_lds<3>(sums, red);   // re-zeroed by thread 0; the step's last barrier orders it
-        if (tid == 0) {
-            const int sf = sums[2] > 0;
-            atomicAdd(&a.counts[0], (unsigned long long)sums[0]);
-            atomicAdd(&a.counts[1], (unsigned long long)(sums[0] > 0));
-            atomicAdd(&a.counts[2], (unsigned long long)sums[1]);
-            atomicAdd(&a.counts[3], 1ull);
-            atomicAdd(&a.counts[4], (unsigned long long)a.T);
-            atomicAdd(&a.counts[5], (unsigned long long)sf);
-            if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-            if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, 0);
-        }
+        if (tid == 0) frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
         __syncthreads();
     }
 }

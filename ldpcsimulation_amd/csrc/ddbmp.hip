@@ -24,7 +24,7 @@
 // Compiled with -ffp-contract=off: the additions keep the reference's order and
 // rounding, so fp64 reproduces it bit for bit; fp32 is the same algorithm in float.
 #include "ddbmp.h"
-#include "device_common.h"
+#include "frame.h"
 #include "minsum_common.h"
 
 #include <hip/hip_runtime.h>
@@ -33,19 +33,6 @@
 namespace ldpc {
 
 template <typename F> __device__ __forceinline__ int dneg(F x) { return !(x >= F(0)); }   // sgn(x) == -1
-
-// One frame's accounting, thread 0 (w, unc: block totals; it: iterations as the reference counts them).
-__device__ __forceinline__ void ddbmp_account(const DecodeArgs &a, int b, int w, int unc, int synd, int it)
-{
-    atomicAdd(&a.counts[0], (unsigned long long)w);
-    atomicAdd(&a.counts[1], (unsigned long long)(w > 0));
-    atomicAdd(&a.counts[2], (unsigned long long)unc);
-    atomicAdd(&a.counts[3], 1ull);
-    atomicAdd(&a.counts[4], (unsigned long long)it);   // totalIterations += it (:230)
-    atomicAdd(&a.counts[5], (unsigned long long)synd);
-    if (w > 0 && a.hist) atomicAdd(&a.hist[w - 1], 1ull);
-    if (a.frame_res) a.frame_res[b] = make_int4(w, unc, synd, it);
-}
 
 // ---------------------------------------------------------------------
 // Generic: one workgroup per codeword, every valid graph. State: mem[E] in column (nlist)
@@ -59,16 +46,10 @@ __device__ __forceinline__ void ddbmp_codeword(const DecodeArgs &a, const DevGra
     const int tid = threadIdx.x, nt = blockDim.x;
     const int N = g.N, M = g.M, T = a.T;
     [[maybe_unused]] const uint32_t nef = (uint32_t)M * (uint32_t)g.dcs;   // LDPC_CHK bound
-    const uint64_t cw = a.first_cw + (uint64_t)b;
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     // ---- channel + front-end (:174-185), initialisation (:301-310) ----
     int unc = 0;
-    auto init_bit = [&](int v, F yv) {
+    channel_bits<F, SRC, true>(a, b, N, cvec, a.y_out, [&](int v, F yv) {
         const F q = front_end<F>(yv, a);
         const int r = q > F(0) ? 1 : -1;
         const int cv = cvec ? cvec[v] : 1;
@@ -82,30 +63,7 @@ __device__ __forceinline__ void ddbmp_codeword(const DecodeArgs &a, const DevGra
             mem[e] = q;
             ef[LDPC_CHK((ref >> 6) * (uint32_t)g.dcs + (ref & 63u), nef, CHK_DDBMP_EDGE)] = flags;
         }
-    };
-    if (SRC == SRC_GIVEN) {
-        const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-        for (int v = tid; v < N; v += nt) init_bit(v, y[v]);
-    } else {
-        const F sigma = (F)a.sigma;
-        const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-        for (int g4 = tid; g4 * 4 < N; g4 += nt) {
-            uint32_t u[4];
-            philox4x32_10<true>((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int v = g4 * 4 + q4;
-                if (v < N) {
-                    const F yv = (F)(cvec ? cvec[v] : 1) * (F(1) + sigma * n[q4]);
-                    if (a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv;
-                    init_bit(v, yv);
-                }
-            }
-        }
-    }
+    });
     if (tid == 0) {
         fl[0] = 0;
         fl[1] = 0;
@@ -178,7 +136,8 @@ __device__ __forceinline__ void ddbmp_codeword(const DecodeArgs &a, const DevGra
     }
     int sums[2] = {wgt, unc};
     block_sum_n_t0<2>(sums, red);
-    if (tid == 0) ddbmp_account(a, b, sums[0], sums[1], synd, cnt);
+    if (tid == 0)   // totalIterations += it (:230)
+        frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], synd, cnt, cnt);
     __syncthreads();
 }
 
@@ -307,20 +266,13 @@ __global__ __launch_bounds__(NT) void k_ddbmp_rows(DecodeArgs a, DevGraph g, uns
                 if (k < deg[q]) ef[LDPC_CHK(slot(q, k), NEF, CHK_DDBMP_EDGE)] = (uint8_t)(((nm >> k) & 1u) | (uint32_t)(dn << 1));
         }
     };
-    const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
 
     // Codewords: blockIdx.x first, then tickets; thread 0 draws the next ticket while the
     // current codeword decodes.
     unsigned nxt = 0;
     if (tid == 0) nxt = gridDim.x + atomicAdd(ticket, 1u);
     for (int b = blockIdx.x; b < a.batch;) {
-        const uint64_t cw = a.first_cw + (uint64_t)b;
-        const int8_t *cvec = nullptr;
-        if (SRC == SRC_GIVEN) {
-            if (a.c) cvec = a.c + (size_t)b * N;
-        } else if (a.cw_table) {
-            cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-        }
+        const int8_t *cvec = frame_codeword<SRC>(a, b, N);
         // ---- channel + front-end (:174-185), initialisation (:301-310), as ddbmp_codeword ----
         F yq[BPT], mem[BPT][DVM];
         int d[BPT];
@@ -332,24 +284,7 @@ __global__ __launch_bounds__(NT) void k_ddbmp_rows(DecodeArgs a, DevGraph g, uns
         }
         if (own) {
             F yv[BPT];
-            if (SRC == SRC_GIVEN) {
-                const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-                for (int q = 0; q < BPT; ++q) yv[q] = (v0 + q < N) ? y[v0 + q] : F(1);
-            } else {
-                uint32_t u[4];
-                philox4x32_10<true>((uint32_t)tid, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-                F n[4];
-                box_muller(u[0], u[1], n[0], n[1]);
-                box_muller(u[2], u[3], n[2], n[3]);
-                const F sigma = (F)a.sigma;
-#pragma unroll
-                for (int q = 0; q < BPT; ++q) {
-                    const int v = v0 + q;
-                    yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-                    if (a.y_out && v < N) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv[q];
-                }
-            }
+            channel_group<F, SRC, true>(a, b, tid, N, cvec, a.y_out, yv);
 #pragma unroll
             for (int q = 0; q < BPT; ++q) {
                 const int v = v0 + q;
@@ -476,7 +411,7 @@ __global__ __launch_bounds__(NT) void k_ddbmp_rows(DecodeArgs a, DevGraph g, uns
         int sums[2] = {wgt, unc};
         block_sum_n_t0<2>(sums, red);
         if (tid == 0) {
-            ddbmp_account(a, b, sums[0], sums[1], synd, cnt);
+            frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], synd, cnt, cnt);
             red[32] = (int)nxt;
         }
         __syncthreads();

@@ -1,6 +1,7 @@
-// device_common.h -- device helpers shared by the decoder kernels
-// (the min-sum kernel files kernels.hip, rows.hip, flood.hip, layered.hip, rows_fast.hip, rows_pp.hip;
-// gdbf.hip: GDBF / NGDBF bit flipping).
+// device_common.h -- device helpers shared by the decoder kernels: Philox + Box-Muller and
+// the block sums. Included by rows.hip, rows_fast.hip, rows_pp.hip and nb.hip, which keep
+// their own channel steps, and through frame.h by every other decoder: kernels.hip,
+// flood.hip, layered.hip, bp.hip, gdbf.hip, ddbmp.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -54,15 +55,24 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 #if LDPC_BM_OCML != 0 && !defined(LDPC_AB_BUILD)
 #error "LDPC_BM_OCML changes the noise the parity tests pin: variant builds only"
 #endif
+// box_muller_hw is the hardware transform under a name of its own: the NGDBF perturbations
+// (gdbf.hip; the noise of src/decodeGDBF.cpp:318-333) take it in every build, so both GDBF
+// kernels decode identical perturbations whatever the channel's transform.
+__device__ __forceinline__ void box_muller_hw(uint32_t ua, uint32_t ur, float &n0, float &n1)
+{
+    const float a = (float)ua * 2.3283064365386963e-10f + 1.1641532182693481e-10f;   // (0, 1]
+    const float r = (float)ur * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
+    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(r));   // sqrt(-2 ln r)
+    n0 = rad * __builtin_amdgcn_cosf(a);
+    n1 = rad * __builtin_amdgcn_sinf(a);
+}
 __device__ __forceinline__ void box_muller(uint32_t ua, uint32_t ur, float &n0, float &n1)
 {
-    const float a = (float)ua * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
-    const float r = (float)ur * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
     if constexpr (!LDPC_BM_OCML) {
-        const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(r));
-        n0 = rad * __builtin_amdgcn_cosf(a);
-        n1 = rad * __builtin_amdgcn_sinf(a);
+        box_muller_hw(ua, ur, n0, n1);
     } else {
+        const float a = (float)ua * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
+        const float r = (float)ur * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
         const float rad = sqrtf(-2.0f * logf(r));
         float s, c;
         sincospif(2.0f * a, &s, &c);

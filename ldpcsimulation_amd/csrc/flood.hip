@@ -1,6 +1,7 @@
 // flood.hip -- flooding min-sum of codes whose state exceeds LDS: the persistent kernel
 // (k_decode_flood) and the phase-per-launch kernels (k_flood_*), their plan and launch.
 #include "minsum_kernels.h"
+#include "frame.h"
 
 namespace ldpc {
 
@@ -43,50 +44,17 @@ __global__ __launch_bounds__(512, (sizeof(F) == 4 && DC <= 8) ? 8 : 4) void k_de
     }
 
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
-        const uint64_t cw = a.first_cw + (uint64_t)b;
-        const int8_t *cvec = nullptr;
-        if (SRC == SRC_GIVEN) {
-            if (a.c) cvec = a.c + (size_t)b * N;
-        } else if (a.cw_table) {
-            cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-        }
+        const int8_t *cvec = frame_codeword<SRC>(a, b, N);
         // ---- channel + front-end (:214-238) into storage order ----
         int unc = 0;
-        if (SRC == SRC_GIVEN) {
-            const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-            for (int v = tid; v < N; v += nt) {
-                const F q = front_end<F>(y[v], a);
-                const int p = fs.pos_of_bit[v];
-                yq[p] = q;
-                app[p] = q;
-                const int cv = cvec ? cvec[v] : 1;
-                unc += ((q > F(0) ? 1 : -1) * cv < 0);
-            }
-        } else {
-            const F sigma = (F)a.sigma;
-            const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-            for (int g4 = tid; g4 * 4 < N; g4 += nt) {
-                uint32_t u[4];
-                philox4x32_10((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-                F n[4];
-                box_muller(u[0], u[1], n[0], n[1]);
-                box_muller(u[2], u[3], n[2], n[3]);
-#pragma unroll
-                for (int q4 = 0; q4 < 4; ++q4) {
-                    const int v = g4 * 4 + q4;
-                    if (v < N) {
-                        const int cv = cvec ? cvec[v] : 1;
-                        const F yv = (F)cv * (F(1) + sigma * n[q4]);
-                        if (a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv;
-                        const F q = front_end<F>(yv, a);
-                        const int p = fs.pos_of_bit[v];
-                        yq[p] = q;
-                        app[p] = q;
-                        unc += ((q > F(0) ? 1 : -1) * cv < 0);
-                    }
-                }
-            }
-        }
+        channel_bits<F, SRC, false>(a, b, N, cvec, a.y_out, [&](int v, F yv) {
+            const F q = front_end<F>(yv, a);
+            const int p = fs.pos_of_bit[v];
+            yq[p] = q;
+            app[p] = q;
+            const int cv = cvec ? cvec[v] : 1;
+            unc += ((q > F(0) ? 1 : -1) * cv < 0);
+        });
         for (int i = tid; i < MP; i += nt) {   // c2v_old = +0: v2c = yq on the first pass (:364-370)
             F2 z;
             z.x = F(0);
@@ -184,23 +152,10 @@ __global__ __launch_bounds__(512, (sizeof(F) == 4 && DC <= 8) ? 8 : 4) void k_de
         }
         int sums[3] = {w, unc, synd};
         block_sum_n_t0<3>(sums, red + 32);
-        if (tid == 0) {
-            const int sf = sums[2] > 0;
-            acc[0] += (unsigned long long)sums[0];
-            acc[1] += (unsigned long long)(sums[0] > 0);
-            acc[2] += (unsigned long long)sums[1];
-            acc[3] += 1ull;
-            acc[5] += (unsigned long long)sf;
-            if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-            if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, 0);
-        }
+        if (tid == 0) frame_account_acc(acc, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0);
         __syncthreads();
     }
-    if (tid == 0 && acc[3] > 0) {
-        acc[4] = acc[3] * (unsigned long long)a.T;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) atomicAdd(&a.counts[q], acc[q]);
-    }
+    if (tid == 0) frame_flush(a.counts, acc, a.T);
 }
 
 static size_t flood_slot_bytes(const DevGraph &g, const FloodSched &fs, bool f64)
@@ -254,36 +209,12 @@ __global__ __launch_bounds__(256) void k_flood_init(DecodeArgs a, DevGraph g, Fl
     if (b >= a.batch) return;
     const auto S = FloodSlot::at<F>(scratch, slot_bytes, r, fs);
     const int N = g.N, NP = fs.ngroups * 64, MP = fs.M_pad;
-    const uint64_t cw = a.first_cw + (uint64_t)b;
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     int unc = 0;
     if (t * 4 < N) {   // ---- channel + front-end (:214-238) into storage order ----
         F yv[4];
-        if (SRC == SRC_GIVEN) {
-            const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) yv[q] = (t * 4 + q < N) ? y[t * 4 + q] : F(1);
-        } else {
-            uint32_t u[4];
-            philox4x32_10((uint32_t)t, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, (uint32_t)a.seed,
-                          (uint32_t)(a.seed >> 32), u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-            const F sigma = (F)a.sigma;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int v = t * 4 + q;
-                yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-                if (v < N && a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv[q];
-            }
-        }
+        channel_group<F, SRC, false>(a, b, t, N, cvec, a.y_out, yv);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int v = t * 4 + q;
@@ -541,13 +472,7 @@ __global__ __launch_bounds__(256) void k_flood_finish(DecodeArgs a, DevGraph g, 
         const auto S = FloodSlot::at<F>(scratch, slot_bytes, r, fs);
         int w = 0, par = 0;
         if (t < N) {
-            const uint64_t cw = a.first_cw + (uint64_t)b;
-            const int8_t *cvec = nullptr;
-            if (a.src == SRC_GIVEN) {
-                if (a.c) cvec = a.c + (size_t)b * N;
-            } else if (a.cw_table) {
-                cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-            }
+            const int8_t *cvec = a.src == SRC_GIVEN ? frame_codeword<SRC_GIVEN>(a, b, N) : frame_codeword<SRC_PHILOX>(a, b, N);
             const int d = S.app[LDPC_CHK(fs.pos_of_bit[t], fs.ngroups * 64 + 1, CHK_FLOOD_APP)] > F(0) ? 1 : -1;   // :471-474
             w = d != (cvec ? cvec[t] : 1);
             if (a.d_out) a.d_out[(size_t)b * N + t] = (int8_t)d;
@@ -575,15 +500,7 @@ __global__ __launch_bounds__(256) void k_flood_account(DecodeArgs a, int b0, int
 {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= nres) return;
-    const int b = b0 + r, w = wsum[r], uc = unc[r], sf = ssum[r] > 0;
-    atomicAdd(&a.counts[0], (unsigned long long)w);
-    atomicAdd(&a.counts[1], (unsigned long long)(w > 0));
-    atomicAdd(&a.counts[2], (unsigned long long)uc);
-    atomicAdd(&a.counts[3], 1ull);
-    atomicAdd(&a.counts[4], (unsigned long long)a.T);
-    atomicAdd(&a.counts[5], (unsigned long long)sf);
-    if (w > 0 && a.hist) atomicAdd(&a.hist[w - 1], 1ull);
-    if (a.frame_res) a.frame_res[b] = make_int4(w, uc, sf, 0);
+    frame_account(a.counts, a.hist, a.frame_res, b0 + r, wsum[r], unc[r], ssum[r] > 0, a.T, 0);
 }
 
 // Messages between the phases: the packed row state (default) or the c2v

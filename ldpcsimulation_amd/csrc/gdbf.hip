@@ -23,7 +23,7 @@
 // Compiled with -ffp-contract=off: E is accumulated with the reference's
 // operation order, so fp64 decisions equal the reference's for the same noise.
 #include "gdbf.h"
-#include "device_common.h"
+#include "frame.h"
 #include "minsum_common.h"
 
 #include <hip/hip_runtime.h>
@@ -94,24 +94,10 @@ __device__ __forceinline__ F gdbf_objective(const DevGraph &g, const int8_t *d, 
     return f;
 }
 
-// NGDBF perturbation normals (the noise of :318-333, which the reference draws
-// from glibc random() by Box-Muller, rand.h:19-20): Box-Muller on the hardware
-// transcendentals -- v_log_f32 (log2), v_sqrt_f32, v_sin_f32 / v_cos_f32 (which
-// take revolutions, so 2*pi*a needs no multiply) -- instead of OCML's correctly
-// rounded logf / sqrtf / sincospif: a few ulp of error in a random perturbation
-// leaves its distribution unchanged, and it is ~10x fewer instructions (the
-// accurate form was ~80 % of the parallel-flip iteration). Both GDBF kernels use
-// it, so they decode identical perturbations; parity with the reference's own
-// perturbation draws goes through the caller-given path (SRC_GIVEN).
-__device__ __forceinline__ void pert_normals(uint32_t ua, uint32_t ur, float &n0, float &n1)
-{
-    const float a = (float)ua * 2.3283064365386963e-10f + 1.1641532182693481e-10f;   // (0, 1]
-    const float r = (float)ur * 2.3283064365386963e-10f + 1.1641532182693481e-10f;
-    const float rad = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(r));   // sqrt(-2 ln r)
-    n0 = rad * __builtin_amdgcn_cosf(a);
-    n1 = rad * __builtin_amdgcn_sinf(a);
-}
-
+// The NGDBF perturbation normals (the noise of :318-333, which the reference draws from
+// glibc random() by Box-Muller, rand.h:19-20) are box_muller_hw's (device_common.h) in both
+// kernels: the accurate OCML form was ~80 % of the parallel-flip iteration. Parity with the
+// reference's own perturbation draws goes through the caller-given path (SRC_GIVEN).
 template <typename F, int SRC>
 __device__ __forceinline__ void gdbf_codeword(const GdbfArgs &a, const DevGraph &g, int b, F *yq, F *theta,
                                               int16_t *dsum, int8_t *d, int8_t *s, int *red, F *redE, int *redI,
@@ -121,34 +107,13 @@ __device__ __forceinline__ void gdbf_codeword(const GdbfArgs &a, const DevGraph 
     const int N = g.N, M = g.M, T = a.T;
     const uint64_t cw = a.first_cw + (uint64_t)b;
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     const bool smooth = (a.flags & GDBF_SMOOTH) != 0;
     // ---- channel + front-end (:251-274) ----
     int unc = 0;
     for (int g4 = tid; g4 * 4 < N; g4 += nt) {
         F yv[4];
-        if (SRC == SRC_GIVEN) {
-            const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) yv[q] = (g4 * 4 + q < N) ? y[g4 * 4 + q] : F(1);
-        } else {
-            uint32_t u[4];
-            philox4x32_10<true>((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-            const F sigma = (F)a.sigma;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int v = g4 * 4 + q;
-                yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-            }
-        }
+        channel_group<F, SRC, true>(a, b, g4, N, cvec, nullptr, yv);
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int v = g4 * 4 + q;
@@ -210,8 +175,8 @@ __device__ __forceinline__ void gdbf_codeword(const GdbfArgs &a, const DevGraph 
                             pv[q] = sizeof(F) == 8 ? ((F)u[q] + F(0.5)) * (F)0x1p-32 : ((F)(u[q] >> 8) + F(0.5)) * (F)0x1p-24;
                     } else {
                         float n[4];
-                        pert_normals(u[0], u[1], n[0], n[1]);
-                        pert_normals(u[2], u[3], n[2], n[3]);
+                        box_muller_hw(u[0], u[1], n[0], n[1]);
+                        box_muller_hw(u[2], u[3], n[2], n[3]);
 #pragma unroll
                         for (int q = 0; q < 4; ++q) pv[q] = nsig * (F)n[q];
                     }
@@ -301,17 +266,8 @@ __device__ __forceinline__ void gdbf_codeword(const GdbfArgs &a, const DevGraph 
     }
     int sums[3] = {wgt, unc, synd};
     block_sum_n_t0<3>(sums, red);
-    if (tid == 0) {
-        const int sf = sums[2] > 0;
-        atomicAdd(&a.counts[0], (unsigned long long)sums[0]);
-        atomicAdd(&a.counts[1], (unsigned long long)(sums[0] > 0));
-        atomicAdd(&a.counts[2], (unsigned long long)sums[1]);
-        atomicAdd(&a.counts[3], 1ull);
-        atomicAdd(&a.counts[4], (unsigned long long)it);   // totalIterations += it (:399)
-        atomicAdd(&a.counts[5], (unsigned long long)sf);
-        if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-        if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, it);
-    }
+    if (tid == 0)   // totalIterations += it (:399)
+        frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, it, it);
     __syncthreads();
 }
 
@@ -486,12 +442,7 @@ __global__ __launch_bounds__(NT, NT != 512 ? 4 : sizeof(F) == 4 ? LDPC_GDBF_ROWS
     if (LDPC_GDBF_TICKETS && tid == 0) nxt = gridDim.x + atomicAdd(a.ticket, 1u);
     for (int b = blockIdx.x; b < a.batch;) {
         const uint64_t cw = a.first_cw + (uint64_t)b;
-        const int8_t *cvec = nullptr;
-        if (SRC == SRC_GIVEN) {
-            if (a.c) cvec = a.c + (size_t)b * N;
-        } else if (a.cw_table) {
-            cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-        }
+        const int8_t *cvec = frame_codeword<SRC>(a, b, N);
         // ---- channel + front-end (:251-274), as gdbf_codeword ----
         F yq[BPT], theta[BPT];
         int d[BPT], dsum[BPT];
@@ -505,23 +456,7 @@ __global__ __launch_bounds__(NT, NT != 512 ? 4 : sizeof(F) == 4 ? LDPC_GDBF_ROWS
         }
         if (own) {
             F yv[BPT];
-            if (SRC == SRC_GIVEN) {
-                const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-#pragma unroll
-                for (int q = 0; q < BPT; ++q) yv[q] = (v0 + q < N) ? y[v0 + q] : F(1);
-            } else {
-                uint32_t u[4];
-                philox4x32_10<true>((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-                F n[4];
-                box_muller(u[0], u[1], n[0], n[1]);
-                box_muller(u[2], u[3], n[2], n[3]);
-                const F sigma = (F)a.sigma;
-#pragma unroll
-                for (int q = 0; q < BPT; ++q) {
-                    const int v = v0 + q;
-                    yv[q] = (F)(v < N && cvec ? cvec[v] : 1) * (F(1) + sigma * n[q]);
-                }
-            }
+            channel_group<F, SRC, true>(a, b, g4, N, cvec, nullptr, yv);
 #pragma unroll
             for (int q = 0; q < BPT; ++q) {
                 const int v = v0 + q;
@@ -582,8 +517,8 @@ __global__ __launch_bounds__(NT, NT != 512 ? 4 : sizeof(F) == 4 ? LDPC_GDBF_ROWS
                     philox4x32_10<true>((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32),
                                   (a.stream_id & 0xFFFFFu) | ((uint32_t)(it + 1) << 20), k0, k1, u);
                     float n[4];
-                    pert_normals(u[0], u[1], n[0], n[1]);
-                    pert_normals(u[2], u[3], n[2], n[3]);
+                    box_muller_hw(u[0], u[1], n[0], n[1]);
+                    box_muller_hw(u[2], u[3], n[2], n[3]);
 #pragma unroll
                     for (int q = 0; q < BPT; ++q) pv[q] = nsig * (F)n[q];
                 }
@@ -674,16 +609,8 @@ __global__ __launch_bounds__(NT, NT != 512 ? 4 : sizeof(F) == 4 ? LDPC_GDBF_ROWS
         }
         int sums[3] = {wgt, unc, synd};
         block_sum_n_t0<3>(sums, red);
-        if (tid == 0) {
-            const int sf = sums[2] > 0;
-            atomicAdd(&a.counts[0], (unsigned long long)sums[0]);
-            atomicAdd(&a.counts[1], (unsigned long long)(sums[0] > 0));
-            atomicAdd(&a.counts[2], (unsigned long long)sums[1]);
-            atomicAdd(&a.counts[3], 1ull);
-            atomicAdd(&a.counts[4], (unsigned long long)it);   // totalIterations += it (:399)
-            atomicAdd(&a.counts[5], (unsigned long long)sf);
-            if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-            if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, it);
+        if (tid == 0) {   // totalIterations += it (:399)
+            frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, it, it);
             if (LDPC_GDBF_TICKETS) red[64] = (int)nxt;
         }
         __syncthreads();

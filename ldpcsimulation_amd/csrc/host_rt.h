@@ -163,6 +163,8 @@ struct CtxCore {
     bool timed = false;
     Options opts;                                  // kernel-selection options (set_option), tests and A/B only
     DevBuf counts;
+    // the codeword ticket: the eighth counter word (above), of which a launch uses 32 bits
+    unsigned *ticket() const { return reinterpret_cast<unsigned *>((unsigned long long *)counts.p + (kCountWords - 1)); }
 
     int init(int dev, int batch)
     {

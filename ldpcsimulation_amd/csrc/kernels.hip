@@ -20,9 +20,9 @@
 // The translation unit is compiled with -ffp-contract=off (see Makefile):
 // no FMA may fuse the channel's 1 + sigma*n or the quantiser.
 #include "minsum_kernels.h"
+#include "frame.h"
 
 namespace ldpc {
-
 
 // ---------------------------------------------------------------------
 // One codeword, all T iterations. rows/app/yq may live in LDS or in a
@@ -34,49 +34,17 @@ __device__ __forceinline__ void decode_codeword(const DecodeArgs &a, const DevGr
 {
     const int tid = threadIdx.x, nt = blockDim.x;
     const int N = g.N, M = g.M;
-    const uint64_t cw = a.first_cw + (uint64_t)b;
 
     // ---- channel + front-end (:214-238) ----
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     int unc = 0;
-    if (SRC == SRC_GIVEN) {
-        const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-        for (int v = tid; v < N; v += nt) {
-            const F q = front_end<F>(y[v], a);
-            yq[v] = q;
-            app[v] = q;
-            const int cv = cvec ? cvec[v] : 1;
-            unc += ((q > F(0) ? 1 : -1) * cv < 0);
-        }
-    } else {
-        const F sigma = (F)a.sigma;
-        const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-        for (int g4 = tid; g4 * 4 < N; g4 += nt) {
-            uint32_t u[4];
-            philox4x32_10((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int v = g4 * 4 + q4;
-                if (v < N) {
-                    const int cv = cvec ? cvec[v] : 1;
-                    const F yv = (F)cv * (F(1) + sigma * n[q4]);
-                    if (a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv;
-                    const F q = front_end<F>(yv, a);
-                    yq[v] = q;
-                    app[v] = q;
-                    unc += ((q > F(0) ? 1 : -1) * cv < 0);
-                }
-            }
-        }
-    }
+    channel_bits<F, SRC, false>(a, b, N, cvec, a.y_out, [&](int v, F yv) {
+        const F q = front_end<F>(yv, a);
+        yq[v] = q;
+        app[v] = q;
+        const int cv = cvec ? cvec[v] : 1;
+        unc += ((q > F(0) ? 1 : -1) * cv < 0);
+    });
     for (int j = tid; j < M; j += nt) {
         RowState<F> z;
         z.m1 = F(0); z.m2 = F(0); z.meta = 0;
@@ -161,19 +129,8 @@ __device__ __forceinline__ void decode_codeword(const DecodeArgs &a, const DevGr
     }
     int sums[3] = {w, unc, synd};
     block_sum_n_t0<3>(sums, red);
-    if (tid == 0) {   // the block totals exist in thread 0 only
-        w = sums[0];
-        unc = sums[1];
-        synd = sums[2];
-        atomicAdd(&a.counts[0], (unsigned long long)w);
-        atomicAdd(&a.counts[1], (unsigned long long)(w > 0));
-        atomicAdd(&a.counts[2], (unsigned long long)unc);
-        atomicAdd(&a.counts[3], 1ull);
-        atomicAdd(&a.counts[4], (unsigned long long)a.T);
-        atomicAdd(&a.counts[5], (unsigned long long)(synd > 0));
-        if (w > 0 && a.hist) atomicAdd(&a.hist[w - 1], 1ull);
-        if (a.frame_res) a.frame_res[b] = make_int4(w, unc, synd > 0 ? 1 : 0, 0);
-    }
+    if (tid == 0)   // the block totals exist in thread 0 only
+        frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
     __syncthreads();
 }
 

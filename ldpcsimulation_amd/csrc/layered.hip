@@ -1,5 +1,6 @@
 // layered.hip -- layered (row-serial) min-sum: k_decode_layered_lds / _global, plan and launch.
 #include "minsum_kernels.h"
+#include "frame.h"
 
 namespace ldpc {
 
@@ -91,40 +92,13 @@ __device__ __forceinline__ int channel_to_storage(const DecodeArgs &a, const Dev
                                                   int b, const int8_t *cvec, const LayApp<F, SPLIT> &app,
                                                   [[maybe_unused]] int np1)
 {
-    const int tid = threadIdx.x, nt = blockDim.x, N = g.N;
-    const uint64_t cw = a.first_cw + (uint64_t)b;
     int unc = 0;
-    if (SRC == SRC_GIVEN) {
-        const F *y = reinterpret_cast<const F *>(a.y) + (size_t)b * N;
-        for (int v = tid; v < N; v += nt) {
-            const F q = front_end<F>(y[v], a);
-            app.st(LDPC_CHK(ls.pos_of_bit[v], np1, CHK_FLOOD_APP), q);
-            const int cv = cvec ? cvec[v] : 1;
-            unc += ((q > F(0) ? 1 : -1) * cv < 0);
-        }
-    } else {
-        const F sigma = (F)a.sigma;
-        const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
-        for (int g4 = tid; g4 * 4 < N; g4 += nt) {
-            uint32_t u[4];
-            philox4x32_10((uint32_t)g4, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
-            F n[4];
-            box_muller(u[0], u[1], n[0], n[1]);
-            box_muller(u[2], u[3], n[2], n[3]);
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const int v = g4 * 4 + q4;
-                if (v < N) {
-                    const int cv = cvec ? cvec[v] : 1;
-                    const F yv = (F)cv * (F(1) + sigma * n[q4]);
-                    if (a.y_out) reinterpret_cast<F *>(a.y_out)[(size_t)b * N + v] = yv;
-                    const F q = front_end<F>(yv, a);
-                    app.st(LDPC_CHK(ls.pos_of_bit[v], np1, CHK_FLOOD_APP), q);
-                    unc += ((q > F(0) ? 1 : -1) * cv < 0);
-                }
-            }
-        }
-    }
+    channel_bits<F, SRC, false, true>(a, b, g.N, cvec, a.y_out, [&](int v, F yv) {
+        const F q = front_end<F>(yv, a);
+        app.st(LDPC_CHK(ls.pos_of_bit[v], np1, CHK_FLOOD_APP), q);
+        const int cv = cvec ? cvec[v] : 1;
+        unc += ((q > F(0) ? 1 : -1) * cv < 0);
+    });
     return unc;
 }
 
@@ -225,13 +199,7 @@ __device__ __forceinline__ void decode_layered_cw(const DecodeArgs &a, const Dev
     const int tid = threadIdx.x, nt = blockDim.x;
     const int N = g.N, NP = fs.ngroups * 64, MP = ls.M_pad;
     const F alpha = (F)a.alpha, delta = (F)a.delta;
-    const uint64_t cw = a.first_cw + (uint64_t)b;
-    const int8_t *cvec = nullptr;
-    if (SRC == SRC_GIVEN) {
-        if (a.c) cvec = a.c + (size_t)b * N;
-    } else if (a.cw_table) {
-        cvec = a.cw_table + (size_t)(cw % (uint64_t)a.cw_rows) * N;
-    }
+    const int8_t *cvec = frame_codeword<SRC>(a, b, N);
     // ---- channel + front-end (:214-238): app = yq in storage order ----
     const int unc = channel_to_storage<F, SRC, SPLIT>(a, g, ls, b, cvec, app, NP + 1);
     for (int i = tid; i < MP; i += nt) {   // c2v_old = +0 (:364-370)
@@ -312,27 +280,9 @@ __device__ __forceinline__ void decode_layered_cw(const DecodeArgs &a, const Dev
     }
     int sums[3] = {w, unc, synd};
     block_sum_n_t0<3>(sums, red);
-    if (tid == 0) {
-        const int sf = sums[2] > 0;
-        acc[0] += (unsigned long long)sums[0];
-        acc[1] += (unsigned long long)(sums[0] > 0);
-        acc[2] += (unsigned long long)sums[1];
-        acc[3] += 1ull;
-        acc[5] += (unsigned long long)sf;
-        if (sums[0] > 0 && a.hist) atomicAdd(&a.hist[sums[0] - 1], 1ull);
-        if (a.frame_res) a.frame_res[b] = make_int4(sums[0], sums[1], sf, 0);
-    }
+    if (tid == 0) frame_account_acc(acc, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0);
     __syncthreads();
     st.mark(5);
-}
-
-__device__ __forceinline__ void flush_acc(const DecodeArgs &a, unsigned long long *acc)
-{
-    if (threadIdx.x == 0 && acc[3] > 0) {
-        acc[4] = acc[3] * (unsigned long long)a.T;
-#pragma unroll
-        for (int q = 0; q < 6; ++q) atomicAdd(&a.counts[q], acc[q]);
-    }
 }
 
 // LDS offsets of the layered state: app[NP + 1] | pad | m12[M_pad] | meta[M_pad].
@@ -365,7 +315,7 @@ __global__ __launch_bounds__(512) void k_decode_layered_lds(DecodeArgs a, DevGra
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x)
         decode_layered_cw<F, SRC, DC, R, false>(a, g, fs, ls, b, la, m12, meta, red, acc, st);
     st.out(a);
-    flush_acc(a, acc);
+    if (threadIdx.x == 0) frame_flush(a.counts, acc, a.T);
 }
 // State in a global slot; SPLIT (fp64): except the posteriors of layered
 // positions [0, P) (dynamic LDS, (P + 1) * sizeof(F) bytes) -- DVB-S2 keeps
@@ -394,7 +344,7 @@ __global__ __launch_bounds__(NT) void k_decode_layered_global(DecodeArgs a, DevG
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x)
         decode_layered_cw<F, SRC, DC, R, SPLIT>(a, g, fs, ls, b, la, m12, meta, red, acc, st);
     st.out(a);
-    flush_acc(a, acc);
+    if (threadIdx.x == 0) frame_flush(a.counts, acc, a.T);
 }
 
 LDPC_CHECK_TU(layered)

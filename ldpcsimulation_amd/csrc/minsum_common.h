@@ -1,6 +1,8 @@
-// minsum_common.h -- device helpers shared by the min-sum kernels
-// (kernels.hip, rows.hip, flood.hip, layered.hip: generic/row/flood/layered kernels; rows_fast.hip: the
-// fast-path row kernel). Reference: C_implementations/src/decodeMinSum.cpp.
+// minsum_common.h -- device helpers shared by the min-sum kernels: the front-end
+// (quantize, front_end), the row state and the packed adds. Included by kernels.hip,
+// rows.hip, flood.hip and layered.hip (through minsum_kernels.h), by rows_fast.hip and
+// rows_pp.hip, and by gdbf.hip and ddbmp.hip (dinf; DD-BMP shares the front-end).
+// Reference: C_implementations/src/decodeMinSum.cpp.
 #pragma once
 #include "kernels.h"
 #include <hip/hip_runtime.h>
