@@ -14,10 +14,10 @@ CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 LIB       = $(LIBDIR)/libldpc_hip.so
 # the min-sum kernel families that `make variant` rebuilds (one translation unit each)
 MINSUM    = kernels rows flood layered
-OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf ddbmp bp nb nb_api nb_graph api graph)
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf rgdbf ddbmp bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
-            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP
+            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP $(BINDIR)/decodeRSMNGDBF
 
 # VFLAGS (-D switches of the A/B experiments, some of them wrong-result by design) belong
 # to the *variant targets, which build into ab/ with -DLDPC_AB_BUILD; the product refuses
@@ -62,6 +62,7 @@ FLAGS_layered   = $(KERNFLAGS) $(NOSLP)
 FLAGS_rows_fast = $(KERNFLAGS)
 FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
 FLAGS_gdbf      = $(NOSLP)
+FLAGS_rgdbf     = $(NOSLP)
 FLAGS_ddbmp     = $(NOSLP)
 FLAGS_nb        = $(NOSLP)
 HDRS      = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h
@@ -105,6 +106,9 @@ $(BINDIR)/decodeSATGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D thresholdAdaptation -D outputSmoothing -o $@ $< $(CLI_LINK)
 $(BINDIR)/decodeSMGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D outputSmoothing -o $@ $< $(CLI_LINK)
+# re-decoding NGDBF (src/RNGDBF.cpp, C_implementations/Makefile:45-46)
+$(BINDIR)/decodeRSMNGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
+	g++ $(CXXFLAGS) -D redecode -D addNoise -D thresholdAdaptation -D weightSyndromes -D outputSmoothing -D saturateSamples -o $@ $< $(CLI_LINK)
 # single-bit-flip schedules and stochastic flipping (Makefile:24-31)
 $(BINDIR)/decodeSGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D sequentialmode -o $@ $< $(CLI_LINK)

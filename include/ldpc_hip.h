@@ -361,6 +361,52 @@ int  ldpc_gdbf_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_gdb
 /* Kernel chosen for a GDBF cfg ("gdbf_lds" / "gdbf_global") and its LDS bytes. */
 int  ldpc_gdbf_kernel_info(ldpc_ctx *ctx, const ldpc_gdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
 
+/* ---- re-decoding NGDBF (decodeRSMNGDBF) --------------------------------- */
+/* src/RNGDBF.cpp (-D redecode ...): a frame whose decoding attempt ends with
+ * unsatisfied checks is decoded again, up to maxphase times (:277-400). Every
+ * phase starts from the channel hard decision with theta_i = theta and runs up
+ * to T parallel-flip iterations of the GDBF decoder above, with fresh
+ * perturbations. The syndrome weight is per bit, w_i = alpha*Ymax/dv_i with
+ * LDPC_GDBF_WEIGHT (:564-567) and 1 without. flags is a subset of
+ * LDPC_GDBF_NOISE|ADAPT|WEIGHT|SMOOTH|SATURATE (decodeRSMNGDBF sets all five);
+ * another ldpc_gdbf_flag is LDPC_ERR_UNSUPPORTED. T >= 1, maxphase >= 1 and
+ * maxphase*T <= 4094. A failed phase runs exactly T iterations and a satisfied
+ * one fewer, so a frame that reports `iters` iterations ran
+ * min(maxphase, iters / T + 1) phases. */
+typedef struct {
+    int32_t flags;        /* OR of ldpc_gdbf_flag (the five above)        */
+    int32_t precision;    /* ldpc_precision                               */
+    int32_t T;            /* iterations per phase (maximum; early stop)   */
+    int32_t maxphase;     /* decoding attempts per frame (maximum)        */
+    int32_t windowsize;   /* SMOOTH: the last windowsize iterations of a phase */
+    int32_t reserved;     /* 0                                            */
+    double  theta;        /* flip threshold (start value with ADAPT)      */
+    double  lambda;       /* ADAPT: threshold decay                       */
+    double  alpha;        /* WEIGHT: w_i = alpha * ymax / dv_i            */
+    double  noise_scale;  /* perturbation sigma = noise_scale * channel sigma */
+    double  ymax;         /* saturation range; also scales the weight     */
+} ldpc_rgdbf_cfg;
+
+/* As ldpc_gdbf_decode_batch, with pert[batch][maxphase*T][N]: row phase*T + it
+ * is added in iteration it of phase `phase` (required with LDPC_GDBF_NOISE).
+ * d_out and frames[].bit_err are the last phase's; frames[].iters and
+ * counts->iters are sums over the phases. Synchronous. Replaces the frame
+ * body of RNGDBF.cpp main() (:247-404). */
+int  ldpc_rgdbf_decode_batch(ldpc_ctx *ctx, const void *y, const void *pert, int batch, const ldpc_rgdbf_cfg *cfg,
+                             const int8_t *c, int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts);
+/* As ldpc_gdbf_sim_launch; the perturbation of iteration it of phase `phase`
+ * is keyed by stream_id | (phase*T + it + 1) << 20, so phase 0 draws what
+ * ldpc_gdbf_sim_launch draws. stream_id < 2^20. Asynchronous. */
+int  ldpc_rgdbf_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev);
+/* ldpc_rgdbf_sim_launch + counts accumulated into *accum; frames host or device. Synchronous. */
+int  ldpc_rgdbf_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                          ldpc_counts *accum);
+/* Kernel chosen for a cfg ("rgdbf_rows" / "rgdbf_lds" / "rgdbf_global") and its LDS bytes.
+ * Option LDPC_OPT_GDBF_KERNEL at 1 forces the generic kernels here too. */
+int  ldpc_rgdbf_kernel_info(ldpc_ctx *ctx, const ldpc_rgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
+
 /* ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ------ */
 /* Messages are reliabilities over GF(q) (0 = most likely symbol); check
  * nodes are the forward-backward EMS with messages truncated to the nm most

@@ -7,6 +7,7 @@
 // LDPC_ERR_DEVICE with a message in ldpc_last_error().
 #include "ldpc_hip.h"
 #include "gdbf.h"
+#include "rgdbf.h"
 #include "bp.h"
 #include "ddbmp.h"
 #include "nb.h"
@@ -39,7 +40,8 @@ static const char *check_site_name(unsigned s)
         "rows_pp app write", "rows_fast gather (app entry)", "rows_fast scatter (c2v slot)",
         "rows_fast bit read (c2v slot)", "rows_fast app write", "flood/layered bit position",
         "flood c2v / eref slot", "flood packed-state row", "gdbf_rows bit", "gdbf_rows check term slot",
-        "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity"};
+        "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity",
+        "rgdbf_rows bit flag", "rgdbf_rows check parity"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -47,7 +49,8 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     hipError_t e = hipStreamSynchronize(s);
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
-                                              check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp};
+                                              check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
+                                              check_take_rgdbf};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -957,6 +960,151 @@ int ldpc_gdbf_kernel_info(ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, char *name, int
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
     const ldpc::GdbfChoice ch = ldpc::gdbf_choose(c->dg, cfg->precision == LDPC_F64, cfg->flags, c->g->maxdv, c->g->maxdc);
+    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
+    if (lds_bytes) *lds_bytes = ch.lds_bytes;
+    return LDPC_OK;
+}
+
+// ----------------------------------------------------------------- re-decoding NGDBF
+static int rgdbf_check_cfg(const ldpc_rgdbf_cfg *cfg)
+{
+    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
+    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
+        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
+    if (cfg->flags & ~511) return set_err(LDPC_ERR_INVALID, "unknown GDBF flags 0x%x", cfg->flags);
+    if (cfg->flags & ~ldpc::kRgdbfFlags)
+        return set_err(LDPC_ERR_UNSUPPORTED, "the re-decoding decoder takes NOISE|ADAPT|WEIGHT|SMOOTH|SATURATE only");
+    // the reference reads an uninitialised `satisfied` at T 0
+    if (cfg->T < 1) return set_err(LDPC_ERR_INVALID, "T must be >= 1");
+    if (cfg->maxphase < 1) return set_err(LDPC_ERR_INVALID, "maxphase must be >= 1");
+    if ((int64_t)cfg->maxphase * cfg->T > 4094)   // the 12-bit iteration field of the Philox stream word
+        return set_err(LDPC_ERR_INVALID, "maxphase * T must be <= 4094");
+    if ((cfg->flags & (LDPC_GDBF_SATURATE | LDPC_GDBF_WEIGHT)) && !(cfg->ymax > 0))
+        return set_err(LDPC_ERR_INVALID, "saturate/weight need ymax > 0");
+    if ((cfg->flags & LDPC_GDBF_SMOOTH) && (cfg->windowsize < 0 || cfg->windowsize > 32767))
+        return set_err(LDPC_ERR_INVALID, "windowsize out of range");
+    return LDPC_OK;
+}
+
+static void rgdbf_fill(ldpc::RgdbfArgs &a, ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, int batch)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.maxphase = cfg->maxphase;
+    a.flags = cfg->flags;
+    a.windowsize = cfg->windowsize;
+    a.theta0 = cfg->theta;
+    a.lambda = cfg->lambda;
+    a.w = cfg->alpha * cfg->ymax;   // RNGDBF.cpp:566, alpha*Ymax/dv left to right: the kernels divide
+    a.ymax = cfg->ymax;
+    a.qmax = 1.0;
+    a.counts = (unsigned long long *)c->counts.p;
+    a.hist = (unsigned long long *)c->hist.p;
+    a.ticket = c->ticket();
+}
+
+static int rgdbf_run(ldpc_ctx *c, const ldpc::RgdbfArgs &a, bool f64)
+{
+    const ldpc::OptScope os(c->opts);
+    const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, f64, c->g->maxdv, c->g->maxdc);
+    int slots = 0;
+    if (ch.slot_bytes) {
+        slots = std::min(a.batch, 2 * c->num_cus);
+        HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
+    }
+    RC_TRY(c->begin_launch());
+    HIP_TRY(ldpc::rgdbf_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
+    return c->end_launch();
+}
+
+int ldpc_rgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_rgdbf_cfg *cfg,
+                            const int8_t *cw, int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+{
+    if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(rgdbf_check_cfg(cfg));
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    if ((cfg->flags & LDPC_GDBF_NOISE) && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
+    RC_TRY(c->enter());
+    const bool f64 = cfg->precision == LDPC_F64;
+    const int N = c->g->N;
+    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
+    ldpc::RgdbfArgs a;
+    rgdbf_fill(a, c, cfg, batch);
+    a.src = ldpc::SRC_GIVEN;
+    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
+    if (cfg->flags & LDPC_GDBF_NOISE)
+        HIP_TRY(stage_in(pert, nb * (size_t)cfg->T * (size_t)cfg->maxphase * fsz, c->p_stage, c->stream, a.pert));
+    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
+    OutStage d, w;
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    a.d_out = (int8_t *)d.dev;
+    a.frame_res = (int4 *)w.dev;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(rgdbf_run(c, a, f64));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    return c->counts_since(before, counts);
+}
+
+static int rgdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(rgdbf_check_cfg(cfg));
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
+    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
+    RC_TRY(c->enter());
+    ldpc::RgdbfArgs a;
+    rgdbf_fill(a, c, cfg, batch);
+    a.src = ldpc::SRC_PHILOX;
+    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // RNGDBF.cpp:167-168
+    a.sigma = std::sqrt(N0 / 2.0);
+    a.noise_sigma = a.sigma * cfg->noise_scale;               // :308
+    a.seed = seed;
+    a.stream_id = stream_id;
+    a.first_cw = first_cw;
+    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
+    a.cw_rows = c->cw_rows;
+    a.frame_res = (int4 *)frames_dev;
+    return rgdbf_run(c, a, cfg->precision == LDPC_F64);
+}
+
+int ldpc_rgdbf_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    if (frames_dev && !is_device_ptr(frames_dev))
+        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
+    return rgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev);
+}
+
+int ldpc_rgdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                         ldpc_counts *accum)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(rgdbf_check_cfg(cfg));
+    RC_TRY(c->enter());
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    OutStage w;   // batch is checked by rgdbf_sim_impl
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
+    RC_TRY(rgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev));
+    HIP_TRY(w.fetch(c->stream));
+    return c->counts_since(before, accum);
+}
+
+int ldpc_rgdbf_kernel_info(ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes)
+{
+    RC_TRY(rgdbf_check_cfg(cfg));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    const ldpc::OptScope os(c->opts);
+    const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, cfg->precision == LDPC_F64, c->g->maxdv, c->g->maxdc);
     if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
     if (lds_bytes) *lds_bytes = ch.lds_bytes;
     return LDPC_OK;

@@ -38,6 +38,8 @@ enum CheckSite : unsigned {
     CHK_BP_MSG,            // bp_rows: message slot                         (< E + 1)
     CHK_DDBMP_EDGE,        // ddbmp: flag byte of an edge in its row's slot  (< rows * stride)
     CHK_DDBMP_CHECK,       // ddbmp: parity byte of a check                 (< rows)
+    CHK_RGDBF_BIT,         // rgdbf_rows: flag byte a check row gathers     (< np)
+    CHK_RGDBF_PARITY,      // rgdbf_rows: parity byte a bit reads / a row writes (< M + 1)
     CHK_SITES
 };
 
@@ -99,6 +101,7 @@ hipError_t check_take_gdbf(CheckRec *out);
 hipError_t check_take_nb(CheckRec *out);
 hipError_t check_take_bp(CheckRec *out);
 hipError_t check_take_ddbmp(CheckRec *out);
+hipError_t check_take_rgdbf(CheckRec *out);
 #endif
 
 }  // namespace ldpc

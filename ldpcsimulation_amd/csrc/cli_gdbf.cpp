@@ -24,6 +24,12 @@
 //                  philox: channel and perturbations generated on the GPU,
 //                  batched (LDPC_BATCH frames per launch).
 //   LDPC_SEED, LDPC_PRECISION, LDPC_BATCH, LDPC_DEVICE, LDPC_DRY_RUN as cli_minsum.cpp.
+//
+// With -D redecode this is decodeRSMNGDBF (src/RNGDBF.cpp:79-485): `maxphase` follows
+// Ymax on the command line, frames go through ldpc_rgdbf_*, a "Phase histogram:" block
+// follows every incremental result and the final one, and the log line counts
+// smoothingUsed per phase and ends with maxphase. A frame's glibc perturbation rows are
+// contiguous over its phases (a failed phase consumes exactly T rows of N draws).
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -96,6 +102,23 @@ void print_histogram(const std::vector<int> &h)   // printHistogram (:465-472)
         if (h[i] > 0) cout << i + 1 << ":\t" << h[i] << endl;
 }
 
+#ifdef redecode
+// Phases a frame ran, from its total iterations: a failed phase runs exactly T
+// iterations, a satisfied one fewer (native.py rgdbf_phases is the same formula).
+int rgdbf_phases(int iters, int T, int maxphase)
+{
+    const int p = iters / T + 1;
+    return p < maxphase ? p : maxphase;
+}
+// Phases of the frame that end with `it > T - windowsize` (RNGDBF.cpp:388-389): every
+// failed phase when windowsize > 0, and the last phase by its own iteration count.
+int rgdbf_smoothing_used(int iters, int T, int maxphase, int windowsize)
+{
+    const int p = rgdbf_phases(iters, T, maxphase);
+    const int last = iters - (p - 1) * T;
+    return (p - 1) * (windowsize > 0) + (last > T - windowsize);
+}
+#endif
 
 }  // namespace
 
@@ -119,6 +142,9 @@ int main(int argc, char *argv[])
 #endif
 #ifdef saturateSamples
     args.push_back("Ymax");
+#endif
+#ifdef redecode
+    args.push_back("maxphase");
 #endif
     args.push_back("[codeword filename]");
     if ((size_t)argc != args.size() && (size_t)argc != args.size() + 1) {   // :116-123
@@ -196,6 +222,17 @@ int main(int argc, char *argv[])
     cfg.ymax = std::atof(argv[idx++]);
     cout << " Ymax = \t" << cfg.ymax << endl;
 #endif
+#ifdef redecode
+    const int maxphase = std::atoi(argv[idx++]);   // RNGDBF.cpp:153-156
+    cout << " maxphase = \t" << maxphase << endl;
+    if (T < 1 || maxphase < 1 || (long)T * maxphase > 4094) {
+        std::cerr << "ldpc: T >= 1, maxphase >= 1 and maxphase * T <= 4094 are required" << endl;
+        return 1;
+    }
+    const int rows_per_frame = T * maxphase;
+#else
+    const int rows_per_frame = T > 0 ? T : 1;
+#endif
 
     std::vector<std::string> cw_lines;   // :165-172, :230-249
     const bool use_cw = (size_t)argc == args.size() + 1;
@@ -223,6 +260,21 @@ int main(int argc, char *argv[])
     }
     const std::string prec = env_or("LDPC_PRECISION", "f64");   // the reference's double; f32 opt-in
     cfg.precision = prec == "f32" ? LDPC_F32 : LDPC_F64;
+#ifdef redecode
+    ldpc_rgdbf_cfg rcfg;
+    std::memset(&rcfg, 0, sizeof rcfg);
+    rcfg.flags = cfg.flags;
+    rcfg.precision = cfg.precision;
+    rcfg.T = T;
+    rcfg.maxphase = maxphase;
+    rcfg.windowsize = cfg.windowsize;
+    rcfg.theta = cfg.theta;
+    rcfg.lambda = cfg.lambda;
+    rcfg.alpha = cfg.alpha;
+    rcfg.noise_scale = cfg.noise_scale;
+    rcfg.ymax = cfg.ymax;
+    std::vector<int> phase_hist(maxphase, 0);   // RNGDBF.cpp:193
+#endif
     const long long seed = std::atoll(env_or("LDPC_SEED", std::to_string((long long)time(0)).c_str()));
     const int batch = philox ? std::atoi(env_or("LDPC_BATCH", "65536")) : 1;
     const int device = std::atoi(env_or("LDPC_DEVICE", "0"));
@@ -267,15 +319,20 @@ int main(int argc, char *argv[])
     const double noiseSigma = sigma * cfg.noise_scale;   // :296
     if (!philox) {
         y.resize(N);
-        if (noise || qprob) pert.resize((size_t)N * (T > 0 ? T : 1));
+        if (noise || qprob) pert.resize((size_t)N * rows_per_frame);
     }
     long generated = 0;
     bool done = false;
     while (!done) {
         if (philox) {
             ldpc_counts tmp{};
+#ifdef redecode
+            if (ldpc_rgdbf_sim_batch(ctx, SNR, R, &rcfg, (uint64_t)seed, 0u, (uint64_t)generated, batch, res.data(),
+                                     &tmp) != LDPC_OK)
+#else
             if (ldpc_gdbf_sim_batch(ctx, SNR, R, &cfg, (uint64_t)seed, 0u, (uint64_t)generated, batch, res.data(),
                                     &tmp) != LDPC_OK)
+#endif
                 die("simulating batch");
         } else {
             if (use_cw) load_codeword(generated, c_cur);
@@ -296,8 +353,13 @@ int main(int argc, char *argv[])
                 yin = yf.data();
                 pin = (noise || qprob) ? pf.data() : nullptr;
             }
+#ifdef redecode
+            if (ldpc_rgdbf_decode_batch(ctx, yin, pin, 1, &rcfg, use_cw ? c_cur.data() : nullptr, nullptr, res.data(),
+                                        nullptr) != LDPC_OK)
+#else
             if (ldpc_gdbf_decode_batch(ctx, yin, pin, 1, &cfg, use_cw ? c_cur.data() : nullptr, nullptr, res.data(),
                                        nullptr) != LDPC_OK)
+#endif
                 die("decoding frame");
             if (noise)   // advance by the rows the decoder drew (one per iteration run, :318-333)
                 for (long k = 0; k < (long)N * res[0].iters; ++k) (void)g.rann();
@@ -311,8 +373,14 @@ int main(int argc, char *argv[])
                 break;
             }
             const int it = res[f].iters;
+#ifdef redecode
+            const bool satisfied = it < T * maxphase;   // of the last phase: only a frame whose phases all failed runs them all
+            if (cfg.flags & LDPC_GDBF_SMOOTH) smoothingUsed += rgdbf_smoothing_used(it, T, maxphase, cfg.windowsize);
+            phase_hist[rgdbf_phases(it, T, maxphase) - 1]++;   // RNGDBF.cpp:403
+#else
             const bool satisfied = it < T;
             if ((cfg.flags & LDPC_GDBF_SMOOTH) && it > T - cfg.windowsize) smoothingUsed++;   // :371-375
+#endif
             const int newErrors = res[f].bit_err;
             uncodedErrors += res[f].uncoded_bit_err;
             if (newErrors > 0) {   // :380-394
@@ -335,6 +403,10 @@ int main(int argc, char *argv[])
                      << ". Word error=" << wordErrors << ". Uncoded errors = " << uncodedErrors
                      << ", uncBER=" << (double)uncodedErrors / totalBits << "\nError weights:\n";
                 print_histogram(hist);
+#ifdef redecode
+                cout << "Phase histogram:\n";   // RNGDBF.cpp:434-437
+                print_histogram(phase_hist);
+#endif
             }
         }
     }
@@ -342,6 +414,10 @@ int main(int argc, char *argv[])
     cout << "\nFinal result: " << errors << " bit errs in " << totalWords << " words, BER=" << (double)errors / totalBits
          << ". Average iterations = " << (double)totalIterations / totalWords << ". Uncoded errors = " << uncodedErrors
          << ", uncBER=" << (double)uncodedErrors / totalBits << endl;
+#ifdef redecode
+    cout << "Phase histogram:\n" << endl;   // RNGDBF.cpp:453, an empty line after the header
+    print_histogram(phase_hist);
+#endif
 
     std::ofstream of(logfilename.c_str(), std::ios::app);   // :425-452
     const char tab = '\t';
@@ -365,6 +441,9 @@ int main(int argc, char *argv[])
 #endif
 #ifdef saturateSamples
     of << cfg.ymax << tab;
+#endif
+#ifdef redecode
+    of << maxphase << tab;
 #endif
     of << argv[1] << endl;
     of.close();

@@ -1,6 +1,6 @@
 // frame.h -- what a frame is: its transmitted codeword, its channel samples and its
 // counters, for the decoder kernels of kernels.hip, flood.hip, layered.hip, bp.hip,
-// gdbf.hip and ddbmp.hip. Args is DecodeArgs or GdbfArgs (which has no y_out, so y_out is
+// gdbf.hip, rgdbf.hip and ddbmp.hip. Args is DecodeArgs or GdbfArgs (which has no y_out, so y_out is
 // a parameter). rows.hip, rows_fast.hip, rows_pp.hip and nb.hip do not include this: their
 // channel steps are staged through LDS and tuned with their kernels.
 #pragma once

@@ -23,6 +23,7 @@
 // Compiled with -ffp-contract=off: E is accumulated with the reference's
 // operation order, so fp64 decisions equal the reference's for the same noise.
 #include "gdbf.h"
+#include "gdbf_front.h"
 #include "frame.h"
 #include "minsum_common.h"
 
@@ -31,28 +32,6 @@
 #include <cstring>
 
 namespace ldpc {
-
-template <typename F> __device__ __forceinline__ F gabs(F x) { return x < F(0) ? -x : x; }
-__device__ __forceinline__ float gfloor(float x) { return __builtin_floorf(x); }
-__device__ __forceinline__ double gfloor(double x) { return __builtin_floor(x); }
-
-// Front-end of one sample (:254-267): saturation, hard decision r, quantize()
-// (:488-493, whose sgn is y > 0 ? 1 : -1).
-template <typename F>
-__device__ __forceinline__ F gdbf_front(F y, const GdbfArgs &a, int &r)
-{
-    F yq = y;
-    const F ymax = (F)a.ymax;
-    if (a.flags & GDBF_SATURATE)
-        if (gabs(yq) > ymax) yq *= ymax / gabs(yq);
-    r = yq > F(0) ? 1 : -1;
-    if (a.flags & GDBF_QUANTIZE) {
-        const F qmax = (F)a.qmax, lmax = ymax / F(2);
-        const F s = yq > F(0) ? F(1) : F(-1);
-        yq = s * gfloor((gabs(yq) * qmax) / (F(2) * lmax) + F(0.5)) * (F(2) * lmax / qmax);
-    }
-    return yq;
-}
 
 // normalCDF (:66-69) and the nearest of quantizeProbabilities' 8 flipping
 // probabilities by squared distance, first minimum (:564-585).

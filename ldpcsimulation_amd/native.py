@@ -128,6 +128,50 @@ class GdbfConfig:
                         self.lambda_, self.alpha, self.noise_scale, self.ymax, self.qsigma)
 
 
+RGDBF_FLAGS = GDBF_NOISE | GDBF_ADAPT | GDBF_WEIGHT | GDBF_SMOOTH | GDBF_SATURATE   # decodeRSMNGDBF sets all five
+
+
+class _RgdbfCfg(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("precision", C.c_int32), ("T", C.c_int32), ("maxphase", C.c_int32),
+                ("windowsize", C.c_int32), ("reserved", C.c_int32), ("theta", C.c_double), ("lambda_", C.c_double),
+                ("alpha", C.c_double), ("noise_scale", C.c_double), ("ymax", C.c_double)]
+
+
+@dataclass
+class RgdbfConfig:
+    """Re-decoding NGDBF (src/RNGDBF.cpp, decodeRSMNGDBF): up to maxphase attempts of T
+    iterations each, per-bit syndrome weight alpha*ymax/dv; flags a subset of RGDBF_FLAGS."""
+    flags: int = RGDBF_FLAGS
+    T: int = 100
+    maxphase: int = 3
+    theta: float = -0.6
+    lambda_: float = 0.99
+    alpha: float = 0.96
+    noise_scale: float = 0.75
+    ymax: float = 2.5
+    windowsize: int = 16
+    precision: int = 1   # F64, the reference's double (RNGDBF.cpp); F32 = 0 opt-in
+
+    def _c(self) -> _RgdbfCfg:
+        return _RgdbfCfg(self.flags, self.precision, self.T, self.maxphase, self.windowsize, 0, self.theta,
+                         self.lambda_, self.alpha, self.noise_scale, self.ymax)
+
+
+def rgdbf_phases(iters, T: int, maxphase: int):
+    """Phases a frame ran, from its total iterations (int or array): a failed phase runs
+    exactly T iterations and a satisfied one fewer, so phases = min(maxphase, iters // T + 1)."""
+    return np.minimum(maxphase, np.asarray(iters) // T + 1)
+
+
+def rgdbf_smoothing_used(iters, T: int, maxphase: int, windowsize: int):
+    """Phases of a frame that end with it > T - windowsize (RNGDBF.cpp:388-389, counted per
+    phase): every failed phase when windowsize > 0, and the last phase by its own count."""
+    iters = np.asarray(iters)
+    p = rgdbf_phases(iters, T, maxphase)
+    last = iters - (p - 1) * T
+    return (p - 1) * int(windowsize > 0) + (last > T - windowsize)
+
+
 @dataclass
 class DecoderConfig:
     """Runtime form of the reference's compile-time decoder switches."""
@@ -230,6 +274,11 @@ def lib():
         "ldpc_gdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_GdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
                                 i32),
         "ldpc_gdbf_kernel_info": ([vp, C.POINTER(_GdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
+        "ldpc_rgdbf_decode_batch": ([vp, vp, vp, i32, C.POINTER(_RgdbfCfg), vp, vp, vp, C.POINTER(Counts)], i32),
+        "ldpc_rgdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp], i32),
+        "ldpc_rgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
+                                 i32),
+        "ldpc_rgdbf_kernel_info": ([vp, C.POINTER(_RgdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
         "ldpc_nb_graph_create": ([i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], i32),
         "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(vp)], i32),
         "ldpc_nb_graph_info": ([vp] + [C.POINTER(i32)] * 6, i32),
@@ -265,6 +314,7 @@ EXPORTED = ["ldpc_abi_version", "ldpc_f64_nms_fast_division", "ldpc_bp_math_prob
             "ldpc_sim_batch", "ldpc_sim_trace", "ldpc_ctx_last_kernel_ms", "ldpc_ctx_kernel_info", "ldpc_ctx_redo_count",
             "ldpc_ctx_row_sched_info", "ldpc_ctx_set_option", "ldpc_ctx_get_option", "ldpc_nb_ctx_set_option",
             "ldpc_gdbf_decode_batch", "ldpc_gdbf_sim_launch", "ldpc_gdbf_sim_batch", "ldpc_gdbf_kernel_info",
+            "ldpc_rgdbf_decode_batch", "ldpc_rgdbf_sim_launch", "ldpc_rgdbf_sim_batch", "ldpc_rgdbf_kernel_info",
             "ldpc_nb_graph_create", "ldpc_nb_graph_load_alist", "ldpc_nb_graph_info", "ldpc_nb_graph_destroy",
             "ldpc_nb_ctx_create", "ldpc_nb_ctx_set_stream", "ldpc_nb_ctx_destroy", "ldpc_nb_ctx_read_counts",
             "ldpc_nb_ctx_last_kernel_ms", "ldpc_ems_kernel_info", "ldpc_ems_decode_batch", "ldpc_ems_sim_launch",
@@ -520,6 +570,45 @@ class Context:
         name = C.create_string_buffer(32)
         lds = C.c_int()
         _check(lib().ldpc_gdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
+        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+
+    # ---- re-decoding NGDBF (src/RNGDBF.cpp) ----
+    def rgdbf_decode(self, y, pert, cfg: RgdbfConfig, c=None, want_decisions: bool = True):
+        """Decode raw channel samples y[batch, N] with perturbations pert[batch, maxphase*T, N]
+        (row phase*T + it; None without GDBF_NOISE). Returns (d, frames, Counts); iters are
+        sums over the phases (rgdbf_phases gives the phase count)."""
+        N = self.graph.N
+        want = np.float64 if cfg.precision == F64 else np.float32
+        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
+        batch = y.shape[0]
+        if pert is not None:
+            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.maxphase * cfg.T, N)
+        if c is not None:
+            c = np.ascontiguousarray(c, dtype=np.int8)
+        d = np.empty((batch, N), dtype=np.int8) if want_decisions else None
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        _check(lib().ldpc_rgdbf_decode_batch(self._h, _ptr(y), _ptr(pert), batch, C.byref(cfg._c()), _ptr(c),
+                                             _ptr(d), _ptr(fr), C.byref(cnt)))
+        return d, fr, cnt
+
+    def rgdbf_sim_launch(self, ebn0_db: float, R: float, cfg: RgdbfConfig, seed: int, stream_id: int, first_cw: int,
+                         batch: int, frames_dev=None):
+        _check(lib().ldpc_rgdbf_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                           _ptr(frames_dev)))
+
+    def rgdbf_sim_batch(self, ebn0_db: float, R: float, cfg: RgdbfConfig, seed: int, stream_id: int, first_cw: int,
+                        batch: int, want_frames: bool = True):
+        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
+        cnt = Counts()
+        _check(lib().ldpc_rgdbf_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                          _ptr(fr), C.byref(cnt)))
+        return fr, cnt
+
+    def rgdbf_kernel_info(self, cfg: RgdbfConfig) -> dict:
+        name = C.create_string_buffer(32)
+        lds = C.c_int()
+        _check(lib().ldpc_rgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
         return {"kernel": name.value.decode(), "lds_bytes": lds.value}
 
 

@@ -21,8 +21,13 @@ line for each point.
     # DD-BMP (decodeDDBMP: the quantiser always on, early stop; the grid of its sweep script
     # scripts/ddbmp_example_4000.2000.4.244.sh is one such call per (Ymax, Q))
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --variant ddbmp --ymax 1.0 --qbits 3
+    # the GDBF family (decodeMNGDBF ... decodeStochasticNGDBF, and the re-decoding decodeRSMNGDBF):
+    # their stop rule 200 bit / 20|10|5 frame errors, early stop
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --gdbf SMNGDBF --alpha 0.8 --ymax 2.5
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --gdbf RSMNGDBF --alpha 0.96 --ymax 2.5 --maxphase 3
 Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
-BER over coded bits, 4 per GF(16) symbol).
+BER over coded bits, 4 per GF(16) symbol; --gdbf: SNR BER avgIt FER T theta noiseScale lambda alpha windowsize Ymax
+[maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job).
 
 --checkpoint FILE appends each point's running totals after a round at most
 every --checkpoint-interval seconds (default 10; 0 = every round; checkpoint.py); a sweep restarted with the same FILE and settings takes the
@@ -41,6 +46,10 @@ from . import checkpoint, native, sim
 
 VARIANTS = {"ms": native.MS, "nms": native.NMS, "oms": native.OMS, "bp": native.BP,
             "ddbmp": native.DDBMP}
+# --gdbf: the decodeGDBF.cpp targets and the re-decoding decoder (RNGDBF.cpp)
+GDBF_NAMES = list(native.GDBF_VARIANTS) + ["RSMNGDBF"]
+# --gdbf settings left unset take these (native.GdbfConfig's)
+GDBF_DEFAULTS = {"theta": -0.6, "lam": 0.99, "noise_scale": 0.75, "window": 16, "nq": 16, "maxphase": 3, "ymax": 2.5}
 
 
 def parse(argv=None):
@@ -54,7 +63,8 @@ def parse(argv=None):
     p.add_argument("--delta", type=float, default=0.0)
     p.add_argument("--quantize", nargs=2, metavar=("YMAX", "Q"), help="-D quantizeSamples front-end")
     p.add_argument("--saturate", type=float, metavar="YMAX", help="-D saturateSamples front-end")
-    p.add_argument("--ymax", type=float, help="--variant ddbmp: Ymax of its quantiser (required)")
+    p.add_argument("--ymax", type=float, help="--variant ddbmp: Ymax of its quantiser (required); --gdbf: Ymax "
+                                               "(default 2.5; --saturate YMAX is the same setting)")
     p.add_argument("--qbits", type=int, help="--variant ddbmp: Q of its quantiser (required)")
     p.add_argument("--precision", choices=["f32", "f64"], default="f64",
                    help="f64 = the reference's double (default); f32 = the fp32 kernels (opt-in)")
@@ -67,6 +77,14 @@ def parse(argv=None):
     p.add_argument("--min-bit-errors", type=int, default=200)
     p.add_argument("--min-frame-errors", type=int, default=None,
                    help="default 40 (decodeMinSum.cpp:189); BP: 20/10/5 by N (decodeBP.cpp:145-147); EMS: 40")
+    p.add_argument("--gdbf", choices=GDBF_NAMES, metavar="NAME",
+                   help="a decoder of the GDBF family: " + ", ".join(GDBF_NAMES) + " (-T, --alpha, --ymax are reused)")
+    p.add_argument("--theta", type=float, help="--gdbf: flip threshold (default -0.6)")
+    p.add_argument("--lam", type=float, help="--gdbf: threshold adaptation lambda (default 0.99)")
+    p.add_argument("--noise-scale", type=float, help="--gdbf: perturbation sigma / channel sigma (default 0.75)")
+    p.add_argument("--window", type=int, help="--gdbf: output smoothing window (default 16)")
+    p.add_argument("--nq", type=int, help="--gdbf: quantiser levels NQ (default 16)")
+    p.add_argument("--maxphase", type=int, help="--gdbf RSMNGDBF: decoding attempts per frame (default 3)")
     p.add_argument("--ems", action="store_true", help="GF(q) Extended Min-Sum on an NB alist (BASELINE config 5)")
     p.add_argument("--nm", type=int, default=16, help="EMS message truncation")
     p.add_argument("--offset", type=float, default=0.0, help="EMS fill offset")
@@ -89,6 +107,19 @@ def parse(argv=None):
                    help="seconds between checkpoint records (0 = after every round); each record "
                         "all-reduces the point's error-weight histogram")
     a = p.parse_args(argv)
+    gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
+    if a.gdbf:
+        if a.ems or a.schedule != "flooding" or a.variant != "ms":
+            p.error("--gdbf excludes --ems, --schedule layered and --variant")
+        if a.quantize or a.qbits is not None:
+            p.error("--gdbf takes its front-end from --ymax and --nq")
+        if a.maxphase is not None and a.gdbf != "RSMNGDBF":
+            p.error("--maxphase belongs to --gdbf RSMNGDBF")
+        if a.ymax is not None and a.saturate is not None and a.ymax != a.saturate:
+            p.error("--ymax and --saturate are the same setting with --gdbf")
+        return a
+    if gdbf_only:
+        p.error("--" + gdbf_only[0].replace("_", "-") + " belongs to --gdbf")
     if a.variant == "ddbmp":
         if a.ymax is None or a.qbits is None:
             p.error("--variant ddbmp needs --ymax and --qbits (decodeDDBMP: alist R SNR T Ymax Q log)")
@@ -103,12 +134,24 @@ def _checkpoint_config(a) -> dict:
     """Every setting that changes a point's result (not the batch or round sizes,
     the GPU count or the log options: exact_stop makes totals independent of them)."""
     ddbmp = {"ymax": a.ymax, "qbits": a.qbits} if a.variant == "ddbmp" else {}
+    if getattr(a, "gdbf", None):   # only then, so that checkpoints written before --gdbf existed still match
+        ddbmp = {"gdbf": a.gdbf, **_gdbf_settings(a)}
     return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
             "snr": list(a.snr), "T": a.iterations, "variant": a.variant, "alpha": a.alpha, "delta": a.delta,
             "quantize": a.quantize, "saturate": a.saturate, "precision": a.precision, "schedule": a.schedule,
             "min_bit_errors": a.min_bit_errors, "min_frame_errors": a.min_frame_errors, "max_frames": a.max_frames,
             "codewords_md5": checkpoint.file_digest(a.codewords), "ems": a.ems, "nm": a.nm, "offset": a.offset,
             "early_stop": not a.no_early_stop}
+
+
+def _gdbf_settings(a) -> dict:
+    """The --gdbf settings with their defaults filled in."""
+    s = {k: (getattr(a, k) if getattr(a, k) is not None else v) for k, v in GDBF_DEFAULTS.items()}
+    if a.ymax is None and a.saturate is not None:
+        s["ymax"] = a.saturate
+    if a.gdbf != "RSMNGDBF":
+        del s["maxphase"]
+    return s
 
 
 def _run_points(a, ck, rank, n_hist, run_point):
@@ -172,6 +215,8 @@ def main(argv=None) -> int:
         ck.start(seed)
     if a.ems:
         return _ems_sweep(a, seed, world, rank, device, ck)
+    if a.gdbf:
+        return _gdbf_sweep(a, seed, world, rank, device, ck)
     cfg = native.DecoderConfig(variant=VARIANTS[a.variant], T=a.iterations, alpha=a.alpha, delta=a.delta,
                                precision=native.F64 if a.precision == "f64" else native.F32,
                                schedule=native.LAYERED if a.schedule == "layered" else native.FLOODING)
@@ -260,6 +305,63 @@ def _ems_sweep(a, seed, world, rank, device, ck=None) -> int:
 
     _run_points(a, ck, rank, bits, run_point)
     if "WORLD_SIZE" in os.environ:   # a process group exists only under torchrun (torch optional otherwise)
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized():
+            dist.destroy_process_group()
+    return 0
+
+
+def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
+    """One SNR point after the other on a decoder of the GDBF family, frames sharded as
+    above; the family's stop rule (decodeGDBF.cpp:216-226) unless --min-frame-errors is given."""
+    g = native.Graph.from_alist(a.alist)
+    ctx = native.Context(g, device, a.batch)
+    s = _gdbf_settings(a)
+    prec = native.F64 if a.precision == "f64" else native.F32
+    common = dict(T=a.iterations, theta=s["theta"], lambda_=s["lam"], alpha=a.alpha, noise_scale=s["noise_scale"],
+                  ymax=s["ymax"], windowsize=s["window"], precision=prec)
+    if a.gdbf == "RSMNGDBF":
+        cfg = native.RgdbfConfig(flags=native.RGDBF_FLAGS, maxphase=s["maxphase"], **common)
+        batch_fn, launch_fn, info_fn = ctx.rgdbf_sim_batch, ctx.rgdbf_sim_launch, ctx.rgdbf_kernel_info
+    else:
+        cfg = native.GdbfConfig(flags=native.GDBF_VARIANTS[a.gdbf], nq=s["nq"], **common)
+        batch_fn, launch_fn, info_fn = ctx.gdbf_sim_batch, ctx.gdbf_sim_launch, ctx.gdbf_kernel_info
+    extra = [s["theta"], s["noise_scale"], s["lam"], a.alpha, float(s["window"]), s["ymax"]]
+    if a.gdbf == "RSMNGDBF":
+        extra.append(float(s["maxphase"]))
+    min_fe = a.min_frame_errors
+    if min_fe is None:
+        min_fe = 5 if g.N > 50000 else 10 if g.N > 10000 else 20
+    if a.codewords:
+        from .codes import read_codeword_file
+        ctx.set_codewords(read_codeword_file(a.codewords, g.N))
+
+    def run_point(k, snr, resume, on_round):
+        def run_batch(first, n):
+            fr, _ = batch_fn(snr, a.rate, cfg, seed, k, first, n)
+            return fr
+
+        launcher = None
+        if not a.sync:
+            def run_launch(first, n, frames_dev):
+                launch_fn(snr, a.rate, cfg, seed, k, first, n, frames_dev)
+            launcher = sim.AsyncLauncher(ctx, a.batch, run_launch)
+        t0 = time.perf_counter()
+        res = sim.simulate_point(run_batch, g.N, a.iterations, snr, a.batch, a.min_bit_errors, min_fe, a.max_frames,
+                                 device=device, launcher=launcher, first_round=a.first_round, iters_in_frames=True,
+                                 resume=resume, on_round=on_round, on_round_interval=a.checkpoint_interval)
+        dt = time.perf_counter() - t0
+        c = res.counts
+        ran = c["frames"] - (int(resume.acc[3]) if resume else 0)   # frames counted by this run
+        return res, res.log_line(a.alist, extra), {
+            "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, "avg_iters": res.avg_iters, "seconds": dt,
+            "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None, "n_gpus": world,
+            "wilson95": sim.wilson_interval(c["frame_err"], c["frames"]), "precision": a.precision,
+            "gdbf": a.gdbf, "kernel": info_fn(cfg)["kernel"], "rounds": res.rounds,
+            "frames_decoded": res.frames_decoded, "collectives": res.collectives}
+
+    _run_points(a, ck, rank, g.N, run_point)
+    if "WORLD_SIZE" in os.environ:
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized():
             dist.destroy_process_group()

@@ -33,7 +33,9 @@ Which of these binds is a reading of the counters, not a proof: a kernel whose
 largest fraction is well below 1 is latency-bound, and the line says so.
 Reference paths: src/decodeMinSum.cpp:247-263 (configs 1-3), src/decodeGDBF.cpp:517-621
 (config 4), SystemC/NB-LDPC/inc/nodes.h:195-293 (config 5), src/decodeBP.cpp:353-409,
-src/decodeDDBMP.cpp:350-423 (the ddbmp_* lines).
+src/decodeDDBMP.cpp:350-423 (the ddbmp_* lines), src/RNGDBF.cpp:277-400 and :552-577 (the
+rsmngdbf_* lines; c4_rgdbf_single_* is rgdbf_rows doing gdbf_rows' work on config 4: one phase,
+weight 1, for the A/B of the two kernels).
 """
 import argparse
 import csv
@@ -88,6 +90,28 @@ CONFIGS = {
                               batch=65536, snr=4.0, what="DD-BMP on PEG 504x1008, T<=100, Ymax 1.0, Q 3, fp32"),
     "ddbmp_peg1008_f64": dict(kind="minsum", code="PEGReg504x1008.alist", variant="ddbmp", prec="f64", T=100,
                               batch=65536, snr=4.0, what="DD-BMP on PEG 504x1008, T<=100, Ymax 1.0, Q 3, fp64"),
+    # re-decoding NGDBF (src/RNGDBF.cpp), T<=100 per phase, maxphase 3, theta -0.6, noiseScale 0.75, lambda 0.99,
+    # window 16, Ymax 2.5; alpha 1.5 on N=1944 and 0.96 on PEG (the golden runs' settings)
+    "rsmngdbf_1944_f32": dict(kind="rgdbf", code="80211n_1944_r12.alist", prec="f32", T=100, maxphase=3, alpha=1.5,
+                              batch=65536, snr=3.5, what="RSMNGDBF on 802.11n N=1944, T<=100 x 3 phases, fp32"),
+    "rsmngdbf_1944_f64": dict(kind="rgdbf", code="80211n_1944_r12.alist", prec="f64", T=100, maxphase=3, alpha=1.5,
+                              batch=65536, snr=3.5, what="RSMNGDBF on 802.11n N=1944, T<=100 x 3 phases, fp64"),
+    "rsmngdbf_peg1008_f32": dict(kind="rgdbf", code="PEGReg504x1008.alist", prec="f32", T=100, maxphase=3,
+                                 alpha=0.96, batch=65536, snr=3.5,
+                                 what="RSMNGDBF on PEG 504x1008, T<=100 x 3 phases, fp32"),
+    "rsmngdbf_peg1008_f64": dict(kind="rgdbf", code="PEGReg504x1008.alist", prec="f64", T=100, maxphase=3,
+                                 alpha=0.96, batch=65536, snr=3.5,
+                                 what="RSMNGDBF on PEG 504x1008, T<=100 x 3 phases, fp64"),
+    "c4_gdbf_noweight_f32": dict(kind="gdbf", code="80211n_1944_r12.alist", prec="f32", T=100, weight=False,
+                                 batch=65536, snr=3.5, what="config 4 without WEIGHT (weight 1) through gdbf_rows, fp32"),
+    "c4_gdbf_noweight_f64": dict(kind="gdbf", code="80211n_1944_r12.alist", prec="f64", T=100, weight=False,
+                                 batch=65536, snr=3.5, what="config 4 without WEIGHT (weight 1) through gdbf_rows, fp64"),
+    "c4_rgdbf_single_f32": dict(kind="rgdbf", code="80211n_1944_r12.alist", prec="f32", T=100, maxphase=1, alpha=0.8,
+                                weight=False, batch=65536, snr=3.5,
+                                what="config 4 through rgdbf_rows: one phase, weight 1 (gdbf_rows' work), fp32"),
+    "c4_rgdbf_single_f64": dict(kind="rgdbf", code="80211n_1944_r12.alist", prec="f64", T=100, maxphase=1, alpha=0.8,
+                                weight=False, batch=65536, snr=3.5,
+                                what="config 4 through rgdbf_rows: one phase, weight 1 (gdbf_rows' work), fp64"),
 }
 
 PMC_PASSES = [
@@ -136,8 +160,16 @@ class Workload:
         self.bits = self.g.N
         if c["kind"] == "gdbf":
             self.cfg = native.GdbfConfig(T=c["T"], precision=prec)
+            if not c.get("weight", True):
+                self.cfg.flags &= ~native.GDBF_WEIGHT
             self.launch_fn = self.ctx.gdbf_sim_launch
             self.kernel = self.ctx.gdbf_kernel_info(self.cfg)["kernel"]
+        elif c["kind"] == "rgdbf":
+            flags = native.RGDBF_FLAGS if c.get("weight", True) else native.RGDBF_FLAGS & ~native.GDBF_WEIGHT
+            self.cfg = native.RgdbfConfig(flags=flags, T=c["T"], maxphase=c["maxphase"], alpha=c["alpha"],
+                                          precision=prec)
+            self.launch_fn = self.ctx.rgdbf_sim_launch
+            self.kernel = self.ctx.rgdbf_kernel_info(self.cfg)["kernel"]
         else:
             v = {"ms": dict(variant=native.MS), "nms": dict(variant=native.NMS, alpha=1.25),
                  "bp": dict(variant=native.BP),
@@ -188,6 +220,12 @@ def timed(name, reps, lib):
            "wall_mbit_s": w.bits * frames / wall / 1e6 if frames else None,
            "fer": d.get("frame_err", 0) / frames if frames else None,
            "avg_iters": d.get("iters", 0) / frames if frames else None, "frames": frames}
+    if w.c["kind"] == "rgdbf":   # the phase split of the first launch's frames (phases follow from a frame's iterations)
+        import numpy as np
+        out["maxphase"] = w.c["maxphase"]
+        fr, _ = w.ctx.rgdbf_sim_batch(w.c["snr"], 0.5, w.cfg, seed=1, stream_id=0, first_cw=0, batch=w.c["batch"])
+        ph = w.native.rgdbf_phases(fr["iters"], w.c["T"], w.c["maxphase"])
+        out["phase_split"] = [int(x) for x in np.bincount(ph, minlength=w.c["maxphase"] + 1)[1:]]
     m = lds_edges_cycles(w)
     if m:
         out["lds_model_cycles_per_launch"], out["row_sched"] = m
