@@ -41,12 +41,30 @@ CASES = {
     "deg1_f64": ("minsum", "deg1", dict(variant="nms", prec="f64", T=12, batch=64)),
     "deg1_f32": ("minsum", "deg1", dict(variant="ms", prec="f32", T=12, batch=64)),
     "heavy_flood_f64": ("minsum", "heavy", dict(variant="nms", prec="f64", T=7, batch=64, kernel="flood")),
+    # one code per row-degree class of the kernels' DC axis (tests/test_shape_matrix.py): the row kernels of
+    # shape (8, 4, 1), (16, 4, 2) and (32, 4, 2), the DC = 32 flood check node, the DC = 16 and 26 layered kernels
+    "w8_f64": ("minsum", "dc8_cpt4_rpt1", dict(variant="nms", prec="f64", T=10, batch=33)),
+    "w8_f32": ("minsum", "dc8_cpt4_rpt1", dict(variant="nms", prec="f32", T=10, batch=33)),
+    "w16_f64": ("minsum", "dc16_cpt4_rpt2", dict(variant="nms", prec="f64", T=10, batch=33)),
+    "w16_f32": ("minsum", "dc16_cpt4_rpt2", dict(variant="ms", prec="f32", T=10, batch=33)),
+    "w32_f64": ("minsum", "dc32_cpt4_rpt2", dict(variant="ms", prec="f64", T=10, batch=33)),
+    "w32_f32": ("minsum", "dc32_cpt4_rpt2", dict(variant="nms", prec="f32", T=10, batch=33)),
+    "w32_flood_f64": ("minsum", "dc32_cpt4_rpt2", dict(variant="nms", prec="f64", T=7, batch=33, kernel="flood")),
+    "w16_layered_f64": ("minsum", "dc16_cpt4_rpt2", dict(variant="nms", prec="f64", T=6, batch=33, layered=True)),
+    "w32_layered_f32": ("minsum", "dc32_cpt4_rpt2", dict(variant="nms", prec="f32", T=6, batch=33, layered=True)),
+    # sim_batch at an odd batch: no sample output, so the plain (straight-line) channel step of each row kernel
+    "plain_rows_pp_f64": ("minsum", "80211n_1944_r12.alist", dict(variant="nms", prec="f64", T=10, batch=131, plain=True)),
+    "plain_rows_fast_f64": ("minsum", "PEGReg504x1008.alist", dict(variant="nms", prec="f64", T=10, batch=131, plain=True)),
+    "plain_rows_f32": ("minsum", "PEGReg504x1008.alist", dict(variant="nms", prec="f32", T=10, batch=131, plain=True)),
 }
+WIDE = ("dc8_cpt4_rpt1", "dc16_cpt4_rpt2", "dc32_cpt4_rpt2")
 
 
 def _fixtures(tmp):
-    """The degree-1-check and heavy-column codes of tests/test_gpu_parity.py."""
+    """The degree-1-check and heavy-column codes of tests/test_gpu_parity.py, and one code per
+    row-degree class of tests/test_shape_matrix.py."""
     from ldpcsimulation_amd import codes
+    from test_shape_matrix import build_code
     H = codes.read_alist(code_path("PEGReg504x1008.alist"))
     deg1 = os.path.join(tmp, "peg_deg1.alist")
     codes.write_alist(codes.ParityCheck.from_rows(H.N, H.rows + [[5], [17, 900]]), deg1)
@@ -57,7 +75,10 @@ def _fixtures(tmp):
         rows[j] = sorted(set(rows[j]) | {0})
     heavy = os.path.join(tmp, "heavy_col.alist")
     codes.write_alist(codes.ParityCheck.from_rows(N, rows), heavy)
-    return {"deg1": deg1, "heavy": heavy}
+    wide = {name: os.path.join(tmp, name + ".alist") for name in WIDE}
+    for name, path in wide.items():
+        build_code(path, name)
+    return {"deg1": deg1, "heavy": heavy, **wide}
 
 
 def run_cases(lib, out, fixtures):
@@ -89,7 +110,11 @@ def run_cases(lib, out, fixtures):
                 sched = native.LAYERED if s.get("layered") else native.FLOODING
                 cfg = native.DecoderConfig(T=s["T"], precision=prec, schedule=sched, **v)
                 snr = 1.0 if code == "dvbs2_1_2.alist" else 2.0
-                _, d, fr, cnt = ctx.sim_trace(snr, 0.5, cfg, seed=9, stream_id=1, first_cw=100, batch=s["batch"])
+                if s.get("plain"):
+                    fr, cnt = ctx.sim_batch(snr, 0.5, cfg, seed=9, stream_id=1, first_cw=100, batch=s["batch"])
+                    d = None
+                else:
+                    _, d, fr, cnt = ctx.sim_trace(snr, 0.5, cfg, seed=9, stream_id=1, first_cw=100, batch=s["batch"])
                 kern[name] = ctx.kernel_info(cfg)["kernel"]
         res[name + "__counts"] = np.array([int(v) for v in cnt.as_dict().values()], dtype=np.int64)
         res[name + "__frames"] = np.asarray(fr).view(np.int32).reshape(len(fr), -1) if fr is not None else np.zeros(0)
@@ -151,7 +176,14 @@ def test_checked_build_equals_product_on_the_config_codes(tmp_path):
     assert {ka["c1_rows_fast_f64"], ka["c2_rows_pp_f64"], ka["c3_flood_f64"], ka["c3_layered_f64"][:7],
             ka["c4_gdbf_f32"], ka["bp_rows_f64"]} == {"rows_fast", "rows_pp", "flood", "layered", "gdbf_rows",
                                                         "bp_rows"}
+    assert [ka[k] for k in ("w8_f64", "w8_f32", "w16_f64", "w16_f32", "w32_f64", "w32_f32")] == \
+        ["rows_fast", "rows", "rows_fast", "rows", "rows", "rows"]
+    assert (ka["w32_flood_f64"], ka["w16_layered_f64"], ka["w32_layered_f32"]) == ("flood", "layered_lds", "layered_lds")
+    assert [ka[k] for k in ("plain_rows_pp_f64", "plain_rows_fast_f64", "plain_rows_f32")] == \
+        ["rows_pp", "rows_fast", "rows"]
     ra, rb = np.load(a), np.load(b)
     assert sorted(ra.files) == sorted(rb.files)
     for k in ra.files:
         assert np.array_equal(ra[k], rb[k]), k
+    for k in ka:   # the new cases compare frames that fail too
+        assert not k.startswith(("w", "plain")) or ra[k + "__counts"][0] > 0, k
