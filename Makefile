@@ -14,10 +14,11 @@ CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 LIB       = $(LIBDIR)/libldpc_hip.so
 # the min-sum kernel families that `make variant` rebuilds (one translation unit each)
 MINSUM    = kernels rows flood layered
-OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf rgdbf ddbmp bp nb nb_api nb_graph api graph)
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf rgdbf hwgdbf ddbmp bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
-            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP $(BINDIR)/decodeRSMNGDBF
+            $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP $(BINDIR)/decodeRSMNGDBF \
+            $(BINDIR)/NGDBFhw
 
 # VFLAGS (-D switches of the A/B experiments, some of them wrong-result by design) belong
 # to the *variant targets, which build into ab/ with -DLDPC_AB_BUILD; the product refuses
@@ -63,6 +64,7 @@ FLAGS_rows_fast = $(KERNFLAGS)
 FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
 FLAGS_gdbf      = $(NOSLP)
 FLAGS_rgdbf     = $(NOSLP)
+FLAGS_hwgdbf    = $(NOSLP)
 FLAGS_ddbmp     = $(NOSLP)
 FLAGS_nb        = $(NOSLP)
 HDRS      = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h
@@ -109,6 +111,9 @@ $(BINDIR)/decodeSMGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 # re-decoding NGDBF (src/RNGDBF.cpp, C_implementations/Makefile:45-46)
 $(BINDIR)/decodeRSMNGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D redecode -D addNoise -D thresholdAdaptation -D weightSyndromes -D outputSmoothing -D saturateSamples -o $@ $< $(CLI_LINK)
+# fixed-point NGDBF hardware model (src/NGDBFhw.cpp, scripts/demo_NGDBFhw_802_3.sh; no reference Makefile target)
+$(BINDIR)/NGDBFhw: $(CSRC)/cli_hwgdbf.cpp $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
+	g++ $(CXXFLAGS) -o $@ $< $(CLI_LINK)
 # single-bit-flip schedules and stochastic flipping (Makefile:24-31)
 $(BINDIR)/decodeSGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D sequentialmode -o $@ $< $(CLI_LINK)
@@ -164,6 +169,13 @@ gdbfvariant: $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(VARDIR)/libldpc_hip_$(NAME).so \
 	    $(filter-out $(LIBDIR)/obj/gdbf.o,$(OBJS)) $(VARDIR)/obj_$(NAME)/gdbf.o
 
+# NGDBFhw kernel A/B variants: make hwgdbfvariant NAME=x VFLAGS="-DLDPC_HWGDBF_..." -> ab/libldpc_hip_x.so
+hwgdbfvariant: $(OBJS)
+	mkdir -p $(VARDIR)/obj_$(NAME)
+	$(HIPCC) $(HIPFLAGS) $(NOSLP) -DLDPC_AB_BUILD $(VFLAGS) -c -o $(VARDIR)/obj_$(NAME)/hwgdbf.o $(CSRC)/hwgdbf.hip
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $(VARDIR)/libldpc_hip_$(NAME).so \
+	    $(filter-out $(LIBDIR)/obj/hwgdbf.o,$(OBJS)) $(VARDIR)/obj_$(NAME)/hwgdbf.o
+
 # BP kernel A/B variants: make bpvariant NAME=x VFLAGS="-DLDPC_BP_..." -> ab/libldpc_hip_x.so
 bpvariant: $(OBJS)
 	mkdir -p $(VARDIR)/obj_$(NAME)
@@ -198,7 +210,7 @@ ref:
 clean:
 	rm -rf $(LIBDIR) $(BINDIR) oracle/liboracle.so
 
-.PHONY: all checked oracle ref clean clean-ab variant fastvariant ppvariant nbvariant gdbfvariant bpvariant
+.PHONY: all checked oracle ref clean clean-ab variant fastvariant ppvariant nbvariant gdbfvariant bpvariant hwgdbfvariant
 
 # Host-code sanitizer build: graph.cpp (the Tanner-graph compiler), nb_graph.cpp
 # (the NB alist reader, GF tables, slot swizzles), cli_common.h (the CLIs' codeword files)

@@ -407,6 +407,69 @@ int  ldpc_rgdbf_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rg
  * Option LDPC_OPT_GDBF_KERNEL at 1 forces the generic kernels here too. */
 int  ldpc_rgdbf_kernel_info(ldpc_ctx *ctx, const ldpc_rgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
 
+/* ---- fixed-point NGDBF hardware model (NGDBFhw) -------------------------- */
+/* src/NGDBFhw.cpp: channel samples and perturbations are sign-magnitude nq-bit
+ * codes expanded to odd integers Y_i, Q_k in +-(2^nq - 1) (:611-677); the
+ * energy E_i = (1 - 2 d_i) Y_i + Smult * (satisfied checks of bit i) +
+ * Q[i + qpointer] is an integer and bit i flips when E_i <= theta (:565-593),
+ * with lmax = ymax / (2w), NL = 2^nq - 1, Smult = round(NL / lmax) and
+ * theta = unpack(pack(quantize(2.0), +1)) (:174-179; 7 and 15 at the defaults).
+ * The perturbation is a shift register of qlen samples drawn once per frame:
+ * qpointer advances by one per iteration, wraps to 0 at qlen - N and carries
+ * over from phase to phase. Every one of the maxphase phases starts from the
+ * channel decision and runs up to T iterations (early stop); all phases run.
+ * The reference's constants (:48-57, in the comments below) are compile-time
+ * there, so only the defaults are pinned by recorded reference runs; other T,
+ * maxphase, nq and qlen are pinned by the numpy restatement of the tests alone.
+ * The front end (saturate, y / (2w), quantise, pack) runs on the device in
+ * `precision`; F64 reproduces the reference bit for bit. */
+typedef struct {
+    int32_t precision;    /* front end: LDPC_F32 / LDPC_F64            */
+    int32_t T;            /* 600  iterations per phase (early stop)     */
+    int32_t maxphase;     /* 1                                          */
+    int32_t nq;           /* 5    bits per sample, 2..7                 */
+    int32_t qlen;         /* 2648 noise samples per frame, > N          */
+    int32_t reserved;     /* 0                                          */
+    double  w, ymax, noise_scale, theta0;   /* 0.185 1.625 0.95 -0.525 */
+} ldpc_hwgdbf_cfg;
+
+/* Decode `batch` frames of given RAW channel samples y[batch][N] and raw noise
+ * draws q[batch][qlen] (noiseSigma * n; float for F32, double for F64; host or
+ * device). qptr0[batch] (host, int32, or NULL = 0) is each frame's start
+ * pointer, in [0, qlen - N). c (bipolar, NULL = all +1), d_out (bipolar, the
+ * last phase's decisions) and counts as ldpc_decode_batch. frames[].bit_err is
+ * the least error weight over the phases, frames[].iters the least iteration
+ * count (counts->iters sums it), frames[].syndrome_fail whether the last phase
+ * ended unsatisfied, frames[].uncoded_bit_err the channel decision's errors.
+ * iters_run[batch] (host or device, optional): the sum of the phases' iteration
+ * counts, which is what a caller adds to the pointer (mod qlen - N).
+ * qlen <= N is LDPC_ERR_INVALID; a graph whose N + qlen + N + M bytes of state
+ * exceed the 65536-byte LDS bound is LDPC_ERR_UNSUPPORTED. Synchronous.
+ * Replaces the frame body of NGDBFhw.cpp main() (:218-373). */
+int  ldpc_hwgdbf_decode_batch(ldpc_ctx *ctx, const void *y, const void *q, const int32_t *qptr0, int batch,
+                              const ldpc_hwgdbf_cfg *cfg, const int8_t *c, int8_t *d_out, ldpc_frame_result *frames,
+                              int32_t *iters_run, ldpc_counts *counts);
+/* Fused on-device Monte-Carlo of one SNR point: the channel of frame f is the
+ * min-sum path's for the same (seed, frame); noise sample k of a frame is
+ * noise_scale * sigma * n with n from Philox4x32-10 keyed by
+ * (seed; k / 4, frame, stream_id | 1 << 20). Every frame starts at pointer 0.
+ * stream_id < 2^20. Asynchronous; counts accumulate in the context. */
+int  ldpc_hwgdbf_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                            uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev);
+/* ldpc_hwgdbf_sim_launch + counts accumulated into *accum; frames host or device. Synchronous. */
+int  ldpc_hwgdbf_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                           ldpc_counts *accum);
+/* ldpc_hwgdbf_sim_batch that also returns the samples drawn, y_out[batch][N] and
+ * q_out[batch][qlen] (the cfg's precision), and d_out (host or device; any may be NULL). */
+int  ldpc_hwgdbf_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *q_out,
+                           int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *accum);
+/* Kernel chosen for a cfg ("hwgdbf_wave": a wavefront per codeword, "hwgdbf_wg": a
+ * workgroup per codeword; the library takes the one that keeps more waves on a CU, and
+ * option LDPC_OPT_GDBF_KERNEL at 1 forces hwgdbf_wg) and the LDS bytes of a workgroup. The cfg is checked first, also with a NULL context. */
+int  ldpc_hwgdbf_kernel_info(ldpc_ctx *ctx, const ldpc_hwgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
+
 /* ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ------ */
 /* Messages are reliabilities over GF(q) (0 = most likely symbol); check
  * nodes are the forward-backward EMS with messages truncated to the nm most

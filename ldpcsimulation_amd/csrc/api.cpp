@@ -8,6 +8,7 @@
 #include "ldpc_hip.h"
 #include "gdbf.h"
 #include "rgdbf.h"
+#include "hwgdbf.h"
 #include "bp.h"
 #include "ddbmp.h"
 #include "nb.h"
@@ -41,7 +42,8 @@ static const char *check_site_name(unsigned s)
         "rows_fast bit read (c2v slot)", "rows_fast app write", "flood/layered bit position",
         "flood c2v / eref slot", "flood packed-state row", "gdbf_rows bit", "gdbf_rows check term slot",
         "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity",
-        "rgdbf_rows bit flag", "rgdbf_rows check parity"};
+        "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
+        "hwgdbf noise sample"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -50,7 +52,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
-                                              check_take_rgdbf};
+                                              check_take_rgdbf, check_take_hwgdbf};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -69,6 +71,7 @@ struct ldpc_ctx : CtxCore {
     const ldpc_graph *g = nullptr;
     ldpc::DevGraph dg{};
     DevBuf graph, hist, y_stage, c_stage, d_stage, fw_stage, cw_table, gscratch, p_stage;
+    DevBuf hw_ptr_stage, hw_it_stage;                     // NGDBFhw: start pointers in, iterations run out
     int cw_rows = 0;
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
     bool has_rs = false;
@@ -335,7 +338,8 @@ static void ctx_free(ldpc_ctx *c)
 {
     if (!c) return;
     c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
-                &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo});
+                &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
+                &c->hw_ptr_stage, &c->hw_it_stage});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
     if (c->aux.join) (void)hipEventDestroy(c->aux.join);
     if (c->aux.s) (void)hipStreamDestroy(c->aux.s);
@@ -1105,6 +1109,199 @@ int ldpc_rgdbf_kernel_info(ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, char *name, i
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
     const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, cfg->precision == LDPC_F64, c->g->maxdv, c->g->maxdc);
+    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
+    if (lds_bytes) *lds_bytes = ch.lds_bytes;
+    return LDPC_OK;
+}
+
+// ----------------------------------------------------------------- fixed-point NGDBF hardware model
+// N < 0: no graph at hand (kernel_info with a null context), qlen is checked against N later.
+static int hwgdbf_check_cfg(const ldpc_hwgdbf_cfg *cfg, int N)
+{
+    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
+    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
+        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
+    if (cfg->reserved != 0) return set_err(LDPC_ERR_INVALID, "reserved must be 0");
+    if (cfg->T < 1) return set_err(LDPC_ERR_INVALID, "T must be >= 1");
+    if (cfg->maxphase < 1) return set_err(LDPC_ERR_INVALID, "maxphase must be >= 1");
+    if ((int64_t)cfg->maxphase * cfg->T > INT32_MAX) return set_err(LDPC_ERR_INVALID, "maxphase * T overflows");
+    if (cfg->nq < 2 || cfg->nq > 7) return set_err(LDPC_ERR_INVALID, "nq must be in 2..7");
+    if (cfg->qlen < 1) return set_err(LDPC_ERR_INVALID, "qlen must be > N");
+    if (!(cfg->w > 0) || !std::isfinite(cfg->w)) return set_err(LDPC_ERR_INVALID, "w must be > 0");
+    if (!(cfg->ymax > 0) || !std::isfinite(cfg->ymax)) return set_err(LDPC_ERR_INVALID, "ymax must be > 0");
+    // NGDBFhw.cpp reads qprime[i + qpointer] out of bounds there (:583 with :357)
+    if (N >= 0 && cfg->qlen <= N) return set_err(LDPC_ERR_INVALID, "qlen %d must be > N = %d", cfg->qlen, N);
+    return LDPC_OK;
+}
+
+// pack(quantize(2.0), +1) then unpack (NGDBFhw.cpp:178, :640-677), in double.
+static int hwgdbf_theta(double lmax, int nq)
+{
+    const double NL = std::pow(2.0, nq) - 1.0;
+    const long m = (long)std::floor(2.0 * NL / (2.0 * lmax));
+    const long code = m & ((1l << nq) - 1);
+    const int mag = (int)(((code & ((1l << (nq - 1)) - 1)) << 1) | 1);
+    return (code >> (nq - 1)) & 1 ? -mag : mag;
+}
+
+static int hwgdbf_fill(ldpc::HwgdbfArgs &a, ldpc::HwgdbfChoice &ch, ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, int batch)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.maxphase = cfg->maxphase;
+    a.nq = cfg->nq;
+    a.qlen = cfg->qlen;
+    a.two_w = 2.0 * cfg->w;
+    a.ymax = cfg->ymax;
+    a.lmax = cfg->ymax / (2.0 * cfg->w);                          // :175
+    a.theta0 = cfg->theta0;
+    const double NL = std::pow(2.0, cfg->nq) - 1.0;
+    const double sm = std::round(NL / a.lmax);                    // :179
+    if (!(sm >= 0 && sm <= 65535)) return set_err(LDPC_ERR_INVALID, "Smult = round(NL / lmax) = %g out of range", sm);
+    a.smult = (int)sm;
+    a.theta = hwgdbf_theta(a.lmax, cfg->nq);
+    a.counts = (unsigned long long *)c->counts.p;
+    a.hist = (unsigned long long *)c->hist.p;
+    a.ticket = c->ticket();
+    const ldpc::OptScope os(c->opts);
+    ch = ldpc::hwgdbf_choose(c->dg, c->g->E, cfg->qlen);
+    if (!ch.name[0])
+        return set_err(LDPC_ERR_UNSUPPORTED,
+                       "NGDBFhw keeps a codeword in LDS: N + qlen + N + M = %d bytes exceed the bound of %d", ch.cw_bytes,
+                       ldpc::kHwgdbfMaxLds);
+    return LDPC_OK;
+}
+
+static int hwgdbf_run(ldpc_ctx *c, const ldpc::HwgdbfArgs &a, const ldpc::HwgdbfChoice &ch, bool f64)
+{
+    RC_TRY(c->begin_launch());
+    HIP_TRY(ldpc::hwgdbf_launch(c->dg, a, f64, ch, c->g->E, c->num_cus, c->stream));
+    return c->end_launch();
+}
+
+int ldpc_hwgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *q, const int32_t *qptr0, int batch,
+                             const ldpc_hwgdbf_cfg *cfg, const int8_t *cw, int8_t *d_out, ldpc_frame_result *frames,
+                             int32_t *iters_run, ldpc_counts *counts)
+{
+    if (!c || !y || !q) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    const int N = c->g->N;
+    if (qptr0 && !is_device_ptr(qptr0))   // a device array is clamped by the kernel
+        for (int b = 0; b < batch; ++b)
+            if (qptr0[b] < 0 || qptr0[b] >= cfg->qlen - N)
+                return set_err(LDPC_ERR_INVALID, "qptr0[%d] = %d outside [0, qlen - N = %d)", b, qptr0[b], cfg->qlen - N);
+    RC_TRY(c->enter());
+    const bool f64 = cfg->precision == LDPC_F64;
+    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
+    ldpc::HwgdbfArgs a;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_fill(a, ch, c, cfg, batch));
+    a.src = ldpc::SRC_GIVEN;
+    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
+    HIP_TRY(stage_in(q, (size_t)batch * cfg->qlen * fsz, c->p_stage, c->stream, a.q));
+    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
+    HIP_TRY(stage_in(qptr0, sizeof(int32_t) * (size_t)batch, c->hw_ptr_stage, c->stream, a.qptr0));
+    OutStage d, w, ir;
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    HIP_TRY(ir.bind(iters_run, c->hw_it_stage, sizeof(int32_t) * (size_t)batch));
+    a.d_out = (int8_t *)d.dev;
+    a.frame_res = (int4 *)w.dev;
+    a.iters_run = (int32_t *)ir.dev;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(hwgdbf_run(c, a, ch, f64));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    HIP_TRY(ir.fetch(c->stream));
+    return c->counts_since(before, counts);
+}
+
+static int hwgdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *q_out, int8_t *d_out,
+                           ldpc_frame_result *frames_dev)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
+    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
+    RC_TRY(c->enter());
+    ldpc::HwgdbfArgs a;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_fill(a, ch, c, cfg, batch));
+    a.src = ldpc::SRC_PHILOX;
+    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // NGDBFhw.cpp:127-129
+    a.sigma = std::sqrt(N0 / 2.0);
+    a.noise_sigma = a.sigma * cfg->noise_scale;
+    a.seed = seed;
+    a.stream_id = stream_id;
+    a.first_cw = first_cw;
+    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
+    a.cw_rows = c->cw_rows;
+    a.y_out = y_out;
+    a.q_out = q_out;
+    a.d_out = d_out;
+    a.frame_res = (int4 *)frames_dev;
+    return hwgdbf_run(c, a, ch, cfg->precision == LDPC_F64);
+}
+
+int ldpc_hwgdbf_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    if (frames_dev && !is_device_ptr(frames_dev))
+        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
+    return hwgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames_dev);
+}
+
+int ldpc_hwgdbf_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *q_out, int8_t *d_out,
+                          ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    RC_TRY(c->enter());
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    const size_t fsz = cfg->precision == LDPC_F64 ? 8 : 4, nb = (size_t)batch * c->g->N;
+    OutStage yo, qo, d, w;
+    HIP_TRY(yo.bind(y_out, c->y_stage, nb * fsz));
+    HIP_TRY(qo.bind(q_out, c->p_stage, (size_t)batch * cfg->qlen * fsz));
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    RC_TRY(hwgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, yo.dev, qo.dev, (int8_t *)d.dev,
+                           (ldpc_frame_result *)w.dev));
+    HIP_TRY(yo.fetch(c->stream));
+    HIP_TRY(qo.fetch(c->stream));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    return c->counts_since(before, accum);
+}
+
+int ldpc_hwgdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                          ldpc_counts *accum)
+{
+    return ldpc_hwgdbf_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames,
+                                 accum);
+}
+
+int ldpc_hwgdbf_kernel_info(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes)
+{
+    RC_TRY(hwgdbf_check_cfg(cfg, c ? c->g->N : -1));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    const ldpc::OptScope os(c->opts);
+    const ldpc::HwgdbfChoice ch = ldpc::hwgdbf_choose(c->dg, c->g->E, cfg->qlen);
+    if (!ch.name[0])
+        return set_err(LDPC_ERR_UNSUPPORTED,
+                       "NGDBFhw keeps a codeword in LDS: N + qlen + N + M = %d bytes exceed the bound of %d", ch.cw_bytes,
+                       ldpc::kHwgdbfMaxLds);
     if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
     if (lds_bytes) *lds_bytes = ch.lds_bytes;
     return LDPC_OK;

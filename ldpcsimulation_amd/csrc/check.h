@@ -40,6 +40,9 @@ enum CheckSite : unsigned {
     CHK_DDBMP_CHECK,       // ddbmp: parity byte of a check                 (< rows)
     CHK_RGDBF_BIT,         // rgdbf_rows: flag byte a check row gathers     (< np)
     CHK_RGDBF_PARITY,      // rgdbf_rows: parity byte a bit reads / a row writes (< M + 1)
+    CHK_HWGDBF_BIT,        // hwgdbf: decision byte a check gathers             (< N)
+    CHK_HWGDBF_CHECK,      // hwgdbf: parity byte a bit reads                   (< M)
+    CHK_HWGDBF_NOISE,      // hwgdbf: noise sample i + qpointer a bit reads     (< qlen)
     CHK_SITES
 };
 
@@ -102,6 +105,7 @@ hipError_t check_take_nb(CheckRec *out);
 hipError_t check_take_bp(CheckRec *out);
 hipError_t check_take_ddbmp(CheckRec *out);
 hipError_t check_take_rgdbf(CheckRec *out);
+hipError_t check_take_hwgdbf(CheckRec *out);
 #endif
 
 }  // namespace ldpc

@@ -48,42 +48,6 @@ using std::endl;
 
 namespace {
 
-// glibc random()/srandom() TYPE_3 (x^31 + x^3 + 1 additive feedback), kept
-// in a copyable object so a frame's perturbation rows can be drawn ahead and
-// the stream then advanced by exactly the rows the decoder used.
-struct GlibcRandom {
-    int32_t r[31];
-    int f = 3, b = 0;
-    explicit GlibcRandom(uint32_t seed)
-    {
-        int32_t w = (int32_t)(seed ? seed : 1u);
-        r[0] = w;
-        for (int i = 1; i < 31; ++i) {   // 16807 * w mod (2^31 - 1), Schrage
-            const int32_t hi = w / 127773, lo = w % 127773;
-            w = 16807 * lo - 2836 * hi;
-            if (w < 0) w += 2147483647;
-            r[i] = w;
-        }
-        for (int i = 0; i < 310; ++i) next();
-    }
-    int32_t next()
-    {
-        const uint32_t v = (uint32_t)r[f] + (uint32_t)r[b];
-        r[f] = (int32_t)v;
-        if (++f == 31) f = 0;
-        if (++b == 31) b = 0;
-        return (int32_t)(v >> 1);
-    }
-    double ranf() { return (double)next() / (1.0 + (double)0x7fffffff); }   // rand.h:10-11
-    double ranu() { return (1.0 + (double)next()) / (2.0 + (double)0x7fffffff); }   // rand.h:13-14
-    double rann()                                                            // rand.h:19-20
-    {
-        const double ua = ranf();
-        const double ur = ranf();
-        return std::cos(2.0 * 3.141592654 * ua) * std::sqrt(-2.0 * std::log(1.0 - ur));
-    }
-};
-
 const char *env_or(const char *k, const char *d)
 {
     const char *v = std::getenv(k);

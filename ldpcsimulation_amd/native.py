@@ -157,6 +157,32 @@ class RgdbfConfig:
                          self.lambda_, self.alpha, self.noise_scale, self.ymax)
 
 
+class _HwGdbfCfg(C.Structure):
+    _fields_ = [("precision", C.c_int32), ("T", C.c_int32), ("maxphase", C.c_int32), ("nq", C.c_int32),
+                ("qlen", C.c_int32), ("reserved", C.c_int32), ("w", C.c_double), ("ymax", C.c_double),
+                ("noise_scale", C.c_double), ("theta0", C.c_double)]
+
+
+@dataclass
+class HwGdbfConfig:
+    """Fixed-point NGDBF hardware model (src/NGDBFhw.cpp): nq-bit sign-magnitude samples, an
+    integer energy, and a noise shift register of qlen samples per frame. The defaults are
+    the reference's compile-time constants (:48-57)."""
+    T: int = 600
+    maxphase: int = 1
+    nq: int = 5
+    qlen: int = 2648
+    w: float = 0.185
+    ymax: float = 1.625
+    noise_scale: float = 0.95
+    theta0: float = -0.525
+    precision: int = 1   # front end: F64, the reference's double; F32 = 0 opt-in
+
+    def _c(self) -> _HwGdbfCfg:
+        return _HwGdbfCfg(self.precision, self.T, self.maxphase, self.nq, self.qlen, 0, self.w, self.ymax,
+                          self.noise_scale, self.theta0)
+
+
 def rgdbf_phases(iters, T: int, maxphase: int):
     """Phases a frame ran, from its total iterations (int or array): a failed phase runs
     exactly T iterations and a satisfied one fewer, so phases = min(maxphase, iters // T + 1)."""
@@ -279,6 +305,14 @@ def lib():
         "ldpc_rgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
                                  i32),
         "ldpc_rgdbf_kernel_info": ([vp, C.POINTER(_RgdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
+        "ldpc_hwgdbf_decode_batch": ([vp, vp, vp, vp, i32, C.POINTER(_HwGdbfCfg), vp, vp, vp, vp, C.POINTER(Counts)],
+                                     i32),
+        "ldpc_hwgdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp], i32),
+        "ldpc_hwgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
+                                  i32),
+        "ldpc_hwgdbf_sim_trace": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp, vp, vp, vp,
+                                   C.POINTER(Counts)], i32),
+        "ldpc_hwgdbf_kernel_info": ([vp, C.POINTER(_HwGdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
         "ldpc_nb_graph_create": ([i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], i32),
         "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(vp)], i32),
         "ldpc_nb_graph_info": ([vp] + [C.POINTER(i32)] * 6, i32),
@@ -315,6 +349,8 @@ EXPORTED = ["ldpc_abi_version", "ldpc_f64_nms_fast_division", "ldpc_bp_math_prob
             "ldpc_ctx_row_sched_info", "ldpc_ctx_set_option", "ldpc_ctx_get_option", "ldpc_nb_ctx_set_option",
             "ldpc_gdbf_decode_batch", "ldpc_gdbf_sim_launch", "ldpc_gdbf_sim_batch", "ldpc_gdbf_kernel_info",
             "ldpc_rgdbf_decode_batch", "ldpc_rgdbf_sim_launch", "ldpc_rgdbf_sim_batch", "ldpc_rgdbf_kernel_info",
+            "ldpc_hwgdbf_decode_batch", "ldpc_hwgdbf_sim_launch", "ldpc_hwgdbf_sim_batch", "ldpc_hwgdbf_sim_trace",
+            "ldpc_hwgdbf_kernel_info",
             "ldpc_nb_graph_create", "ldpc_nb_graph_load_alist", "ldpc_nb_graph_info", "ldpc_nb_graph_destroy",
             "ldpc_nb_ctx_create", "ldpc_nb_ctx_set_stream", "ldpc_nb_ctx_destroy", "ldpc_nb_ctx_read_counts",
             "ldpc_nb_ctx_last_kernel_ms", "ldpc_ems_kernel_info", "ldpc_ems_decode_batch", "ldpc_ems_sim_launch",
@@ -609,6 +645,63 @@ class Context:
         name = C.create_string_buffer(32)
         lds = C.c_int()
         _check(lib().ldpc_rgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
+        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+
+    # ---- fixed-point NGDBF hardware model (src/NGDBFhw.cpp) ----
+    def hwgdbf_decode(self, y, q, cfg: HwGdbfConfig, qptr0=None, c=None, want_decisions: bool = True):
+        """Decode raw channel samples y[batch, N] with the raw noise draws q[batch, qlen]
+        (noiseSigma * n) from the start pointers qptr0[batch] (None: 0). Returns (d, frames,
+        iters_run, Counts): frames[].bit_err / iters are the least over the phases, iters_run
+        the sum of the phases' iterations (what a caller adds to the pointer)."""
+        N = self.graph.N
+        want = np.float64 if cfg.precision == F64 else np.float32
+        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
+        batch = y.shape[0]
+        q = np.ascontiguousarray(q, dtype=want).reshape(batch, cfg.qlen)
+        if qptr0 is not None:
+            qptr0 = np.ascontiguousarray(qptr0, dtype=np.int32).reshape(batch)
+        if c is not None:
+            c = np.ascontiguousarray(c, dtype=np.int8)
+        d = np.empty((batch, N), dtype=np.int8) if want_decisions else None
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        run = np.empty(batch, dtype=np.int32)
+        cnt = Counts()
+        _check(lib().ldpc_hwgdbf_decode_batch(self._h, _ptr(y), _ptr(q), _ptr(qptr0), batch, C.byref(cfg._c()),
+                                              _ptr(c), _ptr(d), _ptr(fr), _ptr(run), C.byref(cnt)))
+        return d, fr, run, cnt
+
+    def hwgdbf_sim_launch(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int,
+                          first_cw: int, batch: int, frames_dev=None):
+        _check(lib().ldpc_hwgdbf_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                            _ptr(frames_dev)))
+
+    def hwgdbf_sim_batch(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int, first_cw: int,
+                         batch: int, want_frames: bool = True):
+        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
+        cnt = Counts()
+        _check(lib().ldpc_hwgdbf_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                           _ptr(fr), C.byref(cnt)))
+        return fr, cnt
+
+    def hwgdbf_sim_trace(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int, first_cw: int,
+                         batch: int):
+        """hwgdbf_sim_batch that also returns the samples drawn: (y, q, d, frames, Counts)."""
+        N = self.graph.N
+        want = np.float64 if cfg.precision == F64 else np.float32
+        y = np.empty((batch, N), dtype=want)
+        q = np.empty((batch, cfg.qlen), dtype=want)
+        d = np.empty((batch, N), dtype=np.int8)
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        _check(lib().ldpc_hwgdbf_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                           y.ctypes.data, q.ctypes.data, d.ctypes.data, fr.ctypes.data,
+                                           C.byref(cnt)))
+        return y, q, d, fr, cnt
+
+    def hwgdbf_kernel_info(self, cfg: HwGdbfConfig) -> dict:
+        name = C.create_string_buffer(32)
+        lds = C.c_int()
+        _check(lib().ldpc_hwgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
         return {"kernel": name.value.decode(), "lds_bytes": lds.value}
 
 

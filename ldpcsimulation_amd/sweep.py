@@ -25,9 +25,12 @@ line for each point.
     # their stop rule 200 bit / 20|10|5 frame errors, early stop
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --gdbf SMNGDBF --alpha 0.8 --ymax 2.5
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --gdbf RSMNGDBF --alpha 0.96 --ymax 2.5 --maxphase 3
+    # the fixed-point NGDBF hardware model (NGDBFhw; its constants are the defaults, R = 0.8413 on 802.3an)
+    python -m ldpcsimulation_amd.sweep 802_3_H.alist --rate 0.8413 --snr 4.0 4.25 -T 600 --hwgdbf
 Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
 BER over coded bits, 4 per GF(16) symbol; --gdbf: SNR BER avgIt FER T theta noiseScale lambda alpha windowsize Ymax
-[maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job).
+[maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job;
+--hwgdbf: SNR BER avgIt FER T theta0 noiseScale w Ymax NQ maxphase qlen alist).
 
 --checkpoint FILE appends each point's running totals after a round at most
 every --checkpoint-interval seconds (default 10; 0 = every round; checkpoint.py); a sweep restarted with the same FILE and settings takes the
@@ -50,6 +53,9 @@ VARIANTS = {"ms": native.MS, "nms": native.NMS, "oms": native.OMS, "bp": native.
 GDBF_NAMES = list(native.GDBF_VARIANTS) + ["RSMNGDBF"]
 # --gdbf settings left unset take these (native.GdbfConfig's)
 GDBF_DEFAULTS = {"theta": -0.6, "lam": 0.99, "noise_scale": 0.75, "window": 16, "nq": 16, "maxphase": 3, "ymax": 2.5}
+# --hwgdbf settings left unset take these (NGDBFhw.cpp:48-57, native.HwGdbfConfig's)
+HWGDBF_DEFAULTS = {"w": 0.185, "ymax": 1.625, "noise_scale": 0.95, "theta0": -0.525, "nq": 5, "maxphase": 1,
+                   "qlen": 2648}
 
 
 def parse(argv=None):
@@ -85,6 +91,12 @@ def parse(argv=None):
     p.add_argument("--window", type=int, help="--gdbf: output smoothing window (default 16)")
     p.add_argument("--nq", type=int, help="--gdbf: quantiser levels NQ (default 16)")
     p.add_argument("--maxphase", type=int, help="--gdbf RSMNGDBF: decoding attempts per frame (default 3)")
+    p.add_argument("--hwgdbf", action="store_true",
+                   help="the fixed-point NGDBF hardware model (NGDBFhw): -T, --ymax (default 1.625), --noise-scale "
+                        "(0.95), --nq (bits per sample, 5) and --maxphase (1) are reused")
+    p.add_argument("--w", type=float, help="--hwgdbf: syndrome weight parameter w (default 0.185)")
+    p.add_argument("--theta0", type=float, help="--hwgdbf: noise offset theta0 (default -0.525)")
+    p.add_argument("--qlen", type=int, help="--hwgdbf: noise samples per frame, > N (default 2648)")
     p.add_argument("--ems", action="store_true", help="GF(q) Extended Min-Sum on an NB alist (BASELINE config 5)")
     p.add_argument("--nm", type=int, default=16, help="EMS message truncation")
     p.add_argument("--offset", type=float, default=0.0, help="EMS fill offset")
@@ -108,6 +120,18 @@ def parse(argv=None):
                         "all-reduces the point's error-weight histogram")
     a = p.parse_args(argv)
     gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
+    if a.hwgdbf:
+        if a.gdbf or a.ems or a.schedule != "flooding" or a.variant != "ms":
+            p.error("--hwgdbf excludes --gdbf, --ems, --variant and --schedule layered")
+        if a.quantize or a.qbits is not None or a.saturate is not None:
+            p.error("--hwgdbf takes its front-end from --ymax, --w and --nq")
+        for n in ("theta", "lam", "window"):
+            if getattr(a, n) is not None:
+                p.error("--" + n + " belongs to --gdbf, not to --hwgdbf")
+        return a
+    for n in ("w", "theta0", "qlen"):
+        if getattr(a, n) is not None:
+            p.error("--" + n + " belongs to --hwgdbf")
     if a.gdbf:
         if a.ems or a.schedule != "flooding" or a.variant != "ms":
             p.error("--gdbf excludes --ems, --schedule layered and --variant")
@@ -136,6 +160,8 @@ def _checkpoint_config(a) -> dict:
     ddbmp = {"ymax": a.ymax, "qbits": a.qbits} if a.variant == "ddbmp" else {}
     if getattr(a, "gdbf", None):   # only then, so that checkpoints written before --gdbf existed still match
         ddbmp = {"gdbf": a.gdbf, **_gdbf_settings(a)}
+    if getattr(a, "hwgdbf", False):   # likewise
+        ddbmp = {"hwgdbf": True, **_hwgdbf_settings(a)}
     return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
             "snr": list(a.snr), "T": a.iterations, "variant": a.variant, "alpha": a.alpha, "delta": a.delta,
             "quantize": a.quantize, "saturate": a.saturate, "precision": a.precision, "schedule": a.schedule,
@@ -152,6 +178,11 @@ def _gdbf_settings(a) -> dict:
     if a.gdbf != "RSMNGDBF":
         del s["maxphase"]
     return s
+
+
+def _hwgdbf_settings(a) -> dict:
+    """The --hwgdbf settings with their defaults filled in."""
+    return {k: (getattr(a, k) if getattr(a, k) is not None else v) for k, v in HWGDBF_DEFAULTS.items()}
 
 
 def _run_points(a, ck, rank, n_hist, run_point):
@@ -215,7 +246,7 @@ def main(argv=None) -> int:
         ck.start(seed)
     if a.ems:
         return _ems_sweep(a, seed, world, rank, device, ck)
-    if a.gdbf:
+    if a.gdbf or a.hwgdbf:
         return _gdbf_sweep(a, seed, world, rank, device, ck)
     cfg = native.DecoderConfig(variant=VARIANTS[a.variant], T=a.iterations, alpha=a.alpha, delta=a.delta,
                                precision=native.F64 if a.precision == "f64" else native.F32,
@@ -312,12 +343,22 @@ def _ems_sweep(a, seed, world, rank, device, ck=None) -> int:
 
 
 def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
-    """One SNR point after the other on a decoder of the GDBF family, frames sharded as
-    above; the family's stop rule (decodeGDBF.cpp:216-226) unless --min-frame-errors is given."""
+    """One SNR point after the other on a decoder of the GDBF family (--gdbf NAME) or on the
+    fixed-point hardware model (--hwgdbf), frames sharded as above; the family's stop rule
+    (decodeGDBF.cpp:216-226) unless --min-frame-errors is given."""
     g = native.Graph.from_alist(a.alist)
     ctx = native.Context(g, device, a.batch)
-    s = _gdbf_settings(a)
     prec = native.F64 if a.precision == "f64" else native.F32
+    if a.hwgdbf:
+        s = _hwgdbf_settings(a)
+        cfg = native.HwGdbfConfig(T=a.iterations, maxphase=s["maxphase"], nq=s["nq"], qlen=s["qlen"], w=s["w"],
+                                  ymax=s["ymax"], noise_scale=s["noise_scale"], theta0=s["theta0"], precision=prec)
+        batch_fn, launch_fn, info_fn = ctx.hwgdbf_sim_batch, ctx.hwgdbf_sim_launch, ctx.hwgdbf_kernel_info
+        extra = [s["theta0"], s["noise_scale"], s["w"], s["ymax"], float(s["nq"]), float(s["maxphase"]),
+                 float(s["qlen"])]
+        return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra,
+                            "NGDBFhw")
+    s = _gdbf_settings(a)
     common = dict(T=a.iterations, theta=s["theta"], lambda_=s["lam"], alpha=a.alpha, noise_scale=s["noise_scale"],
                   ymax=s["ymax"], windowsize=s["window"], precision=prec)
     if a.gdbf == "RSMNGDBF":
@@ -329,6 +370,11 @@ def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
     extra = [s["theta"], s["noise_scale"], s["lam"], a.alpha, float(s["window"]), s["ymax"]]
     if a.gdbf == "RSMNGDBF":
         extra.append(float(s["maxphase"]))
+    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra, a.gdbf)
+
+
+def _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra, name) -> int:
+    """The points of a bit-flipping sweep: early stop, so the frames report their iterations."""
     min_fe = a.min_frame_errors
     if min_fe is None:
         min_fe = 5 if g.N > 50000 else 10 if g.N > 10000 else 20
@@ -357,7 +403,7 @@ def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
             "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, "avg_iters": res.avg_iters, "seconds": dt,
             "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None, "n_gpus": world,
             "wilson95": sim.wilson_interval(c["frame_err"], c["frames"]), "precision": a.precision,
-            "gdbf": a.gdbf, "kernel": info_fn(cfg)["kernel"], "rounds": res.rounds,
+            "gdbf": name, "kernel": info_fn(cfg)["kernel"], "rounds": res.rounds,
             "frames_decoded": res.frames_decoded, "collectives": res.collectives}
 
     _run_points(a, ck, rank, g.N, run_point)

@@ -35,7 +35,10 @@ Reference paths: src/decodeMinSum.cpp:247-263 (configs 1-3), src/decodeGDBF.cpp:
 (config 4), SystemC/NB-LDPC/inc/nodes.h:195-293 (config 5), src/decodeBP.cpp:353-409,
 src/decodeDDBMP.cpp:350-423 (the ddbmp_* lines), src/RNGDBF.cpp:277-400 and :552-577 (the
 rsmngdbf_* lines; c4_rgdbf_single_* is rgdbf_rows doing gdbf_rows' work on config 4: one phase,
-weight 1, for the A/B of the two kernels).
+weight 1, for the A/B of the two kernels), src/NGDBFhw.cpp:280-373 and :546-593 (the hwgdbf_*
+lines at the reference's constants and its R = 0.8413; *_wg forces the workgroup-per-codeword
+instance for the A/B of the two kernel shapes; where that is the library's own choice, the
+wavefront shape is measured with --lib on `make hwgdbfvariant VFLAGS=-DLDPC_HWGDBF_FORCE_WAVE`).
 """
 import argparse
 import csv
@@ -113,6 +116,15 @@ CONFIGS = {
                                 weight=False, batch=65536, snr=3.5,
                                 what="config 4 through rgdbf_rows: one phase, weight 1 (gdbf_rows' work), fp64"),
 }
+# fixed-point NGDBF hardware model (src/NGDBFhw.cpp) at the reference's constants: T<=600, one phase, NQ 5,
+# qlen 2648, R 0.8413; 802.3an at 4.0 dB (the golden runs' operating point), PEG 1008 at 6.0 dB
+for _code, _tag, _snr in (("802_3_H.alist", "802_3", 4.0), ("PEGReg504x1008.alist", "peg1008", 6.0)):
+    for _prec in ("f32", "f64"):
+        for _k, _kname in ((0, ""), (1, "_wg")):
+            CONFIGS[f"hwgdbf_{_tag}_{_prec}{_kname}"] = dict(
+                kind="hwgdbf", code=_code, prec=_prec, T=600, batch=65536, snr=_snr, rate=0.8413, gdbf_kernel=_k,
+                what=f"NGDBFhw on {_tag}, T<=600, {_prec} front end, "
+                     f"{'hwgdbf_wg forced' if _k else 'the kernel the library chooses'}")
 
 PMC_PASSES = [
     "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY "
@@ -170,6 +182,12 @@ class Workload:
                                           precision=prec)
             self.launch_fn = self.ctx.rgdbf_sim_launch
             self.kernel = self.ctx.rgdbf_kernel_info(self.cfg)["kernel"]
+        elif c["kind"] == "hwgdbf":
+            self.cfg = native.HwGdbfConfig(T=c["T"], precision=prec)
+            self.ctx.set_option("gdbf_kernel", c["gdbf_kernel"])
+            self.launch_fn = self.ctx.hwgdbf_sim_launch
+            info = self.ctx.hwgdbf_kernel_info(self.cfg)
+            self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
         else:
             v = {"ms": dict(variant=native.MS), "nms": dict(variant=native.NMS, alpha=1.25),
                  "bp": dict(variant=native.BP),
@@ -181,7 +199,7 @@ class Workload:
 
     def launch(self, k, batch=None):
         b = batch or self.c["batch"]
-        self.launch_fn(self.c["snr"], 0.5, self.cfg, seed=1, stream_id=0, first_cw=k * self.c["batch"], batch=b)
+        self.launch_fn(self.c["snr"], self.c.get("rate", 0.5), self.cfg, seed=1, stream_id=0, first_cw=k * self.c["batch"], batch=b)
         return self.ctx.last_kernel_ms()
 
     def counts(self):
@@ -226,6 +244,8 @@ def timed(name, reps, lib):
         fr, _ = w.ctx.rgdbf_sim_batch(w.c["snr"], 0.5, w.cfg, seed=1, stream_id=0, first_cw=0, batch=w.c["batch"])
         ph = w.native.rgdbf_phases(fr["iters"], w.c["T"], w.c["maxphase"])
         out["phase_split"] = [int(x) for x in np.bincount(ph, minlength=w.c["maxphase"] + 1)[1:]]
+    if w.c["kind"] == "hwgdbf":
+        out["lds_bytes_per_workgroup"] = w.lds_bytes
     m = lds_edges_cycles(w)
     if m:
         out["lds_model_cycles_per_launch"], out["row_sched"] = m
