@@ -14,11 +14,11 @@ CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 LIB       = $(LIBDIR)/libldpc_hip.so
 # the min-sum kernel families that `make variant` rebuilds (one translation unit each)
 MINSUM    = kernels rows flood layered
-OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf rgdbf hwgdbf ddbmp bp nb nb_api nb_graph api graph)
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_fast rows_pp gdbf rgdbf rstat hwgdbf ddbmp bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
             $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP $(BINDIR)/decodeRSMNGDBF \
-            $(BINDIR)/NGDBFhw
+            $(BINDIR)/NGDBFhw $(BINDIR)/redecodeStatistics $(BINDIR)/replayGDBF
 
 # VFLAGS (-D switches of the A/B experiments, some of them wrong-result by design) belong
 # to the *variant targets, which build into ab/ with -DLDPC_AB_BUILD; the product refuses
@@ -64,6 +64,7 @@ FLAGS_rows_fast = $(KERNFLAGS)
 FLAGS_rows_pp   = $(KERNFLAGS) $(ALIGNFLAGS) $(PPSCHED)
 FLAGS_gdbf      = $(NOSLP)
 FLAGS_rgdbf     = $(NOSLP)
+FLAGS_rstat     = $(NOSLP)
 FLAGS_hwgdbf    = $(NOSLP)
 FLAGS_ddbmp     = $(NOSLP)
 FLAGS_nb        = $(NOSLP)
@@ -114,6 +115,11 @@ $(BINDIR)/decodeRSMNGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 # fixed-point NGDBF hardware model (src/NGDBFhw.cpp, scripts/demo_NGDBFhw_802_3.sh; no reference Makefile target)
 $(BINDIR)/NGDBFhw: $(CSRC)/cli_hwgdbf.cpp $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -o $@ $< $(CLI_LINK)
+# every attempt of every frame (src/newstat.cpp, src/replayGDBF.cpp; C_implementations/Makefile:39-43)
+$(BINDIR)/redecodeStatistics: $(CSRC)/cli_rstat.cpp $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
+	g++ $(CXXFLAGS) -o $@ $< $(CLI_LINK)
+$(BINDIR)/replayGDBF: $(CSRC)/cli_rstat.cpp $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
+	g++ $(CXXFLAGS) -D replay -o $@ $< $(CLI_LINK)
 # single-bit-flip schedules and stochastic flipping (Makefile:24-31)
 $(BINDIR)/decodeSGDBF: $(GDBF_SRC) $(LIB) $(CSRC)/cli_common.h | $(BINDIR)
 	g++ $(CXXFLAGS) -D sequentialmode -o $@ $< $(CLI_LINK)

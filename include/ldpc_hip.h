@@ -407,6 +407,75 @@ int  ldpc_rgdbf_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rg
  * Option LDPC_OPT_GDBF_KERNEL at 1 forces the generic kernels here too. */
 int  ldpc_rgdbf_kernel_info(ldpc_ctx *ctx, const ldpc_rgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
 
+/* ---- every attempt of every frame (redecodeStatistics, replayGDBF) ------- */
+/* src/newstat.cpp and src/replayGDBF.cpp: a frame is decoded `attempts` times
+ * from the same channel samples, each attempt with perturbations of its own,
+ * and every attempt runs whether or not an earlier one succeeded. An attempt
+ * is exactly one phase of the re-decoding decoder above (maxphase 1): it starts
+ * from the channel hard decision with theta_i = theta and dsum = 0 and runs up
+ * to T iterations with early stop. flags as ldpc_rgdbf_cfg (another
+ * ldpc_gdbf_flag is LDPC_ERR_UNSUPPORTED); 1 <= T <= 4094, attempts >= 1,
+ * first_attempt >= 0, first_attempt + attempts <= 2^31 - 1 and attempts * T
+ * <= 2^31 - 1 (a frame's summed iterations are an int32), else
+ * LDPC_ERR_INVALID. Attempt indices are absolute: local attempt k of a call is
+ * attempt first_attempt + k, so a caller may split the attempts over calls. */
+typedef struct {           /* ldpc_rgdbf_cfg with the attempt range in place of maxphase */
+    int32_t flags, precision, T, attempts, windowsize, first_attempt;
+    double  theta, lambda, alpha, noise_scale, ymax;
+} ldpc_rstat_cfg;
+/* One attempt: the residual error weight (the outcome newstat.cpp logs), the
+ * iterations run, whether the output fails a check, and whether the attempt
+ * ended inside the smoothing window (it > T - windowsize). */
+typedef struct { int32_t bit_err, iters, syndrome_fail, smoothing_used; } ldpc_attempt_result;
+/* Per-iteration traces, each optional, host or device. Row `it` of an attempt
+ * is what replayGDBF.cpp:370-373 prints after iteration it: the decisions after
+ * the flips and the check products that iteration computed before them. The
+ * iteration whose check step finds every check satisfied writes no row. */
+typedef struct {           /* all optional; host or device */
+    int32_t *err_trace;    /* [batch][attempts][T]: bits != codeword after iteration it; -1 not run */
+    int32_t *unsat_trace;  /* [batch][attempts][T]: unsatisfied checks found by iteration it's check step; -1 */
+    int8_t  *d_trace;      /* [batch][attempts][T][N] +-1 after iteration it; 0 not run */
+    int8_t  *s_trace;      /* [batch][attempts][T][M] +-1, the syndrome that iteration used; 0 not run */
+} ldpc_rstat_trace;
+
+/* Decode `batch` frames of given raw channel samples y[batch][N] `attempts`
+ * times each with pert[batch][attempts][T][N] (row (k, it) is added in iteration
+ * it of local attempt k; required with LDPC_GDBF_NOISE). attempts_out
+ * [batch][attempts] (host or device, optional) is the product. frames[] and
+ * counts follow newstat.cpp:421-465: bit_err, syndrome_fail and d_out are the
+ * LAST attempt's, iters the sum over the attempts, uncoded_bit_err is counted
+ * once per frame. trace NULL: none. Synchronous. */
+int  ldpc_rstat_decode_batch(ldpc_ctx *ctx, const void *y, const void *pert, int batch, const ldpc_rstat_cfg *cfg,
+                             const int8_t *c, ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace,
+                             int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts);
+/* Fused Monte-Carlo: the channel of frame f is ldpc_rgdbf_sim_launch's; attempt
+ * a of frame f draws the perturbations that phase 0 of frame f + (a << 32) draws
+ * there (Philox counter (bit / 4, lo32(f), hi32(f) + a, stream_id | (it + 1) << 20)),
+ * so attempt 0 is ldpc_rgdbf_sim_launch with maxphase 1. first_cw + batch <= 2^32
+ * and stream_id < 2^20, else LDPC_ERR_INVALID. attempts_dev, the traces and
+ * frames_dev are device pointers or NULL. Asynchronous. */
+int  ldpc_rstat_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_dev,
+                           const ldpc_rstat_trace *trace_dev, ldpc_frame_result *frames_dev);
+/* ldpc_rstat_sim_launch + counts accumulated into *accum; outputs host or device. Synchronous. */
+int  ldpc_rstat_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_out,
+                          const ldpc_rstat_trace *trace, ldpc_frame_result *frames, ldpc_counts *accum);
+/* ldpc_rstat_sim_batch that also returns the samples drawn, y_out[batch][N] and
+ * pert_out[batch][attempts][T][N] (the cfg's precision; rows that were not drawn
+ * are zero), and d_out (host or device; any may be NULL). */
+int  ldpc_rstat_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *pert_out,
+                          ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace, int8_t *d_out,
+                          ldpc_frame_result *frames, ldpc_counts *accum);
+/* Kernel chosen for a cfg, with or without traces: "rstat_rows" (the codes
+ * rgdbf_rows takes: a persistent workgroup with the graph in registers) or
+ * "rstat_wg" (a workgroup per attempt; lds_bytes 0: its state is in a global
+ * slot). Traces and option LDPC_OPT_GDBF_KERNEL at 1 force rstat_wg. The cfg is
+ * checked first, also with a NULL context. */
+int  ldpc_rstat_kernel_info(ldpc_ctx *ctx, const ldpc_rstat_cfg *cfg, int with_trace, char *name, int name_len,
+                            int *lds_bytes);
+
 /* ---- fixed-point NGDBF hardware model (NGDBFhw) -------------------------- */
 /* src/NGDBFhw.cpp: channel samples and perturbations are sign-magnitude nq-bit
  * codes expanded to odd integers Y_i, Q_k in +-(2^nq - 1) (:611-677); the

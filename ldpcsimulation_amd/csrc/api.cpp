@@ -8,6 +8,7 @@
 #include "ldpc_hip.h"
 #include "gdbf.h"
 #include "rgdbf.h"
+#include "rstat.h"
 #include "hwgdbf.h"
 #include "bp.h"
 #include "ddbmp.h"
@@ -43,7 +44,7 @@ static const char *check_site_name(unsigned s)
         "flood c2v / eref slot", "flood packed-state row", "gdbf_rows bit", "gdbf_rows check term slot",
         "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity",
         "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
-        "hwgdbf noise sample"};
+        "hwgdbf noise sample", "rstat decision byte", "rstat check parity"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -52,7 +53,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
-                                              check_take_rgdbf, check_take_hwgdbf};
+                                              check_take_rgdbf, check_take_hwgdbf, check_take_rstat};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -71,6 +72,7 @@ struct ldpc_ctx : CtxCore {
     const ldpc_graph *g = nullptr;
     ldpc::DevGraph dg{};
     DevBuf graph, hist, y_stage, c_stage, d_stage, fw_stage, cw_table, gscratch, p_stage;
+    DevBuf rs_att_stage, rs_unc, rs_tr_stage[4];          // every-attempt decoders: attempt results, uncoded errors, traces
     DevBuf hw_ptr_stage, hw_it_stage;                     // NGDBFhw: start pointers in, iterations run out
     int cw_rows = 0;
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
@@ -339,7 +341,8 @@ static void ctx_free(ldpc_ctx *c)
     if (!c) return;
     c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
                 &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
-                &c->hw_ptr_stage, &c->hw_it_stage});
+                &c->hw_ptr_stage, &c->hw_it_stage, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
+                &c->rs_tr_stage[2], &c->rs_tr_stage[3]});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
     if (c->aux.join) (void)hipEventDestroy(c->aux.join);
     if (c->aux.s) (void)hipStreamDestroy(c->aux.s);
@@ -1109,6 +1112,245 @@ int ldpc_rgdbf_kernel_info(ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, char *name, i
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
     const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, cfg->precision == LDPC_F64, c->g->maxdv, c->g->maxdc);
+    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
+    if (lds_bytes) *lds_bytes = ch.lds_bytes;
+    return LDPC_OK;
+}
+
+// ----------------------------------------------------------------- every attempt of every frame
+static int rstat_check_cfg(const ldpc_rstat_cfg *cfg)
+{
+    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
+    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
+        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
+    if (cfg->flags & ~511) return set_err(LDPC_ERR_INVALID, "unknown GDBF flags 0x%x", cfg->flags);
+    if (cfg->flags & ~ldpc::kRgdbfFlags)
+        return set_err(LDPC_ERR_UNSUPPORTED, "the every-attempt decoder takes NOISE|ADAPT|WEIGHT|SMOOTH|SATURATE only");
+    // T >= 1 as ldpc_rgdbf_cfg; 4094: the 12-bit iteration field of the Philox stream word
+    if (cfg->T < 1 || cfg->T > 4094) return set_err(LDPC_ERR_INVALID, "T must be in 1..4094");
+    if (cfg->attempts < 1) return set_err(LDPC_ERR_INVALID, "attempts must be >= 1");
+    if (cfg->first_attempt < 0) return set_err(LDPC_ERR_INVALID, "first_attempt must be >= 0");
+    if ((int64_t)cfg->first_attempt + cfg->attempts > INT32_MAX)
+        return set_err(LDPC_ERR_INVALID, "first_attempt + attempts must be <= 2^31 - 1");
+    // a frame's iterations, summed over its attempts, are an int32 (ldpc_frame_result.iters)
+    if ((int64_t)cfg->attempts * cfg->T > INT32_MAX)
+        return set_err(LDPC_ERR_INVALID, "attempts * T must be <= 2^31 - 1");
+    if ((cfg->flags & (LDPC_GDBF_SATURATE | LDPC_GDBF_WEIGHT)) && !(cfg->ymax > 0))
+        return set_err(LDPC_ERR_INVALID, "saturate/weight need ymax > 0");
+    if ((cfg->flags & LDPC_GDBF_SMOOTH) && (cfg->windowsize < 0 || cfg->windowsize > 32767))
+        return set_err(LDPC_ERR_INVALID, "windowsize out of range");
+    return LDPC_OK;
+}
+
+static int rstat_check_batch(ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int batch)
+{
+    if (batch <= 0 || batch > c->max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    if ((int64_t)batch * cfg->attempts > INT32_MAX)
+        return set_err(LDPC_ERR_INVALID, "batch * attempts must be <= 2^31 - 1");
+    return LDPC_OK;
+}
+
+// The outputs of a launch the caller may hold on the host or on the device.
+struct RstatOuts {
+    OutStage att, tr[4];
+};
+
+// Fills the decoder's part of `a`, binds attempts_out and the traces (device_only: an
+// asynchronous launch takes device pointers only) and puts the "not run" values into the traces.
+static int rstat_fill(ldpc::RstatArgs &a, RstatOuts &o, ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int batch,
+                      ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace, bool device_only)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.attempts = cfg->attempts;
+    a.first_attempt = cfg->first_attempt;
+    a.flags = cfg->flags;
+    a.windowsize = cfg->windowsize;
+    a.theta0 = cfg->theta;
+    a.lambda = cfg->lambda;
+    a.w = cfg->alpha * cfg->ymax;   // newstat.cpp symNodeUpdates, alpha*Ymax/dv left to right: the kernels divide
+    a.ymax = cfg->ymax;
+    a.qmax = 1.0;
+    a.counts = (unsigned long long *)c->counts.p;
+    a.hist = (unsigned long long *)c->hist.p;
+    a.ticket = c->ticket();
+    const size_t items = (size_t)batch * cfg->attempts, rows = items * (size_t)cfg->T;
+    void *const tp[4] = {trace ? trace->err_trace : nullptr, trace ? trace->unsat_trace : nullptr,
+                         trace ? trace->d_trace : nullptr, trace ? trace->s_trace : nullptr};
+    if (device_only) {
+        if (attempts_out && !is_device_ptr(attempts_out))
+            return set_err(LDPC_ERR_INVALID, "attempts_out must be a device pointer");
+        for (void *p : tp)
+            if (p && !is_device_ptr(p)) return set_err(LDPC_ERR_INVALID, "the traces must be device pointers");
+    }
+    HIP_TRY(o.att.bind(attempts_out, c->rs_att_stage, sizeof(ldpc_attempt_result) * items));
+    if (!o.att.dev) {
+        HIP_TRY(c->rs_att_stage.ensure(sizeof(ldpc_attempt_result) * items));
+        o.att.dev = c->rs_att_stage.p;
+    }
+    a.attempt_res = (int4 *)o.att.dev;
+    HIP_TRY(c->rs_unc.ensure(sizeof(int) * (size_t)batch));
+    a.frame_unc = (int *)c->rs_unc.p;
+    const size_t tb[4] = {rows * 4, rows * 4, rows * (size_t)c->g->N, rows * (size_t)c->g->M};
+    for (int k = 0; k < 4; ++k) {
+        HIP_TRY(o.tr[k].bind(tp[k], c->rs_tr_stage[k], tb[k]));
+        if (o.tr[k].dev) HIP_TRY(hipMemsetAsync(o.tr[k].dev, k < 2 ? 0xFF : 0, tb[k], c->stream));   // -1 / 0: not run
+    }
+    a.err_trace = (int32_t *)o.tr[0].dev;
+    a.unsat_trace = (int32_t *)o.tr[1].dev;
+    a.d_trace = (int8_t *)o.tr[2].dev;
+    a.s_trace = (int8_t *)o.tr[3].dev;
+    return LDPC_OK;
+}
+
+static int rstat_fetch(ldpc_ctx *c, const RstatOuts &o)
+{
+    HIP_TRY(o.att.fetch(c->stream));
+    for (int k = 0; k < 4; ++k) HIP_TRY(o.tr[k].fetch(c->stream));
+    return LDPC_OK;
+}
+
+static int rstat_run(ldpc_ctx *c, const ldpc::RstatArgs &a, bool f64)
+{
+    const ldpc::OptScope os(c->opts);
+    const bool trace = a.err_trace || a.unsat_trace || a.d_trace || a.s_trace;
+    const ldpc::RstatChoice ch = ldpc::rstat_choose(c->dg, f64, trace, c->g->maxdv, c->g->maxdc);
+    int slots = 0;
+    if (ch.slot_bytes) {
+        slots = (int)std::min<int64_t>((int64_t)a.batch * a.attempts, 2 * c->num_cus);
+        HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
+    }
+    RC_TRY(c->begin_launch());
+    HIP_TRY(ldpc::rstat_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
+    return c->end_launch();
+}
+
+int ldpc_rstat_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_rstat_cfg *cfg,
+                            const int8_t *cw, ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace,
+                            int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+{
+    if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(rstat_check_cfg(cfg));
+    RC_TRY(rstat_check_batch(c, cfg, batch));
+    if ((cfg->flags & LDPC_GDBF_NOISE) && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
+    RC_TRY(c->enter());
+    const bool f64 = cfg->precision == LDPC_F64;
+    const int N = c->g->N;
+    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
+    ldpc::RstatArgs a;
+    RstatOuts o;
+    RC_TRY(rstat_fill(a, o, c, cfg, batch, attempts_out, trace, false));
+    a.src = ldpc::SRC_GIVEN;
+    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
+    if (cfg->flags & LDPC_GDBF_NOISE)
+        HIP_TRY(stage_in(pert, nb * (size_t)cfg->attempts * (size_t)cfg->T * fsz, c->p_stage, c->stream, a.pert));
+    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
+    OutStage d, w;
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    a.d_out = (int8_t *)d.dev;
+    a.frame_res = (int4 *)w.dev;
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(rstat_run(c, a, f64));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    RC_TRY(rstat_fetch(c, o));
+    return c->counts_since(before, counts);
+}
+
+// y_out / pert_out / d_out: device pointers or null.
+static int rstat_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_out,
+                          const ldpc_rstat_trace *trace, bool device_only, RstatOuts &o, void *y_out, void *pert_out,
+                          int8_t *d_out, ldpc_frame_result *frames_dev)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(rstat_check_cfg(cfg));
+    RC_TRY(rstat_check_batch(c, cfg, batch));
+    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
+    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
+    // the attempt index takes the high word of the frame number in the Philox counter
+    if (first_cw > (1ull << 32) - (uint64_t)batch)
+        return set_err(LDPC_ERR_INVALID, "first_cw + batch must be <= 2^32");
+    RC_TRY(c->enter());
+    ldpc::RstatArgs a;
+    RC_TRY(rstat_fill(a, o, c, cfg, batch, attempts_out, trace, device_only));
+    a.src = ldpc::SRC_PHILOX;
+    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // newstat.cpp:192-193
+    a.sigma = std::sqrt(N0 / 2.0);
+    a.noise_sigma = a.sigma * cfg->noise_scale;               // :336
+    a.seed = seed;
+    a.stream_id = stream_id;
+    a.first_cw = first_cw;
+    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
+    a.cw_rows = c->cw_rows;
+    a.y_out = y_out;
+    a.pert_out = pert_out;
+    a.d_out = d_out;
+    a.frame_res = (int4 *)frames_dev;
+    return rstat_run(c, a, cfg->precision == LDPC_F64);
+}
+
+int ldpc_rstat_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_dev,
+                          const ldpc_rstat_trace *trace_dev, ldpc_frame_result *frames_dev)
+{
+    if (frames_dev && !is_device_ptr(frames_dev))
+        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
+    RstatOuts o;
+    return rstat_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, attempts_dev, trace_dev, true, o, nullptr,
+                          nullptr, nullptr, frames_dev);
+}
+
+int ldpc_rstat_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *pert_out,
+                         ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace, int8_t *d_out,
+                         ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(rstat_check_cfg(cfg));
+    RC_TRY(rstat_check_batch(c, cfg, batch));
+    RC_TRY(c->enter());
+    unsigned long long before[kCountWords];
+    RC_TRY(c->read_counts_raw(before));
+    const size_t fsz = cfg->precision == LDPC_F64 ? 8 : 4, nb = (size_t)batch * c->g->N;
+    const size_t pb = nb * (size_t)cfg->attempts * (size_t)cfg->T * fsz;
+    OutStage yo, po, d, w;
+    HIP_TRY(yo.bind(y_out, c->y_stage, nb * fsz));
+    HIP_TRY(po.bind(pert_out, c->p_stage, pb));
+    HIP_TRY(d.bind(d_out, c->d_stage, nb));
+    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
+    if (po.dev) HIP_TRY(hipMemsetAsync(po.dev, 0, pb, c->stream));   // rows that are not drawn
+    RstatOuts o;
+    RC_TRY(rstat_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, attempts_out, trace, false, o, yo.dev,
+                          po.dev, (int8_t *)d.dev, (ldpc_frame_result *)w.dev));
+    HIP_TRY(yo.fetch(c->stream));
+    HIP_TRY(po.fetch(c->stream));
+    HIP_TRY(d.fetch(c->stream));
+    HIP_TRY(w.fetch(c->stream));
+    RC_TRY(rstat_fetch(c, o));
+    return c->counts_since(before, accum);
+}
+
+int ldpc_rstat_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_out,
+                         const ldpc_rstat_trace *trace, ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    return ldpc_rstat_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, attempts_out,
+                                trace, nullptr, frames, accum);
+}
+
+int ldpc_rstat_kernel_info(ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int with_trace, char *name, int name_len,
+                           int *lds_bytes)
+{
+    RC_TRY(rstat_check_cfg(cfg));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    const ldpc::OptScope os(c->opts);
+    const ldpc::RstatChoice ch =
+        ldpc::rstat_choose(c->dg, cfg->precision == LDPC_F64, with_trace != 0, c->g->maxdv, c->g->maxdc);
     if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
     if (lds_bytes) *lds_bytes = ch.lds_bytes;
     return LDPC_OK;

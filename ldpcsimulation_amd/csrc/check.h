@@ -43,6 +43,8 @@ enum CheckSite : unsigned {
     CHK_HWGDBF_BIT,        // hwgdbf: decision byte a check gathers             (< N)
     CHK_HWGDBF_CHECK,      // hwgdbf: parity byte a bit reads                   (< M)
     CHK_HWGDBF_NOISE,      // hwgdbf: noise sample i + qpointer a bit reads     (< qlen)
+    CHK_RSTAT_BIT,         // rstat: decision byte a check gathers (rstat_wg < N, rstat_rows < np)
+    CHK_RSTAT_PARITY,      // rstat: parity byte a bit reads / a row writes (rstat_wg < M, rstat_rows < M + 1)
     CHK_SITES
 };
 
@@ -106,6 +108,7 @@ hipError_t check_take_bp(CheckRec *out);
 hipError_t check_take_ddbmp(CheckRec *out);
 hipError_t check_take_rgdbf(CheckRec *out);
 hipError_t check_take_hwgdbf(CheckRec *out);
+hipError_t check_take_rstat(CheckRec *out);
 #endif
 
 }  // namespace ldpc

@@ -21,6 +21,7 @@
 // Compiled with -ffp-contract=off; E keeps the reference's operation order, and
 // w_i*(+-1) is exactly +-w_i, so the kernels select the sign instead of multiplying.
 #include "rgdbf.h"
+#include "rgdbf_shared.h"
 #include "gdbf_front.h"
 #include "frame.h"
 #include "minsum_common.h"
@@ -31,32 +32,13 @@
 
 namespace ldpc {
 
-// w_i of a bit of degree deg (:564-567): alpha*Ymax (a.w, the host's double product)
-// divided by dv in double, then rounded to F. A bit without checks adds no term.
-template <typename F>
-__device__ __forceinline__ F rgdbf_weight(const RgdbfArgs &a, int deg)
-{
-    if (!(a.flags & GDBF_WEIGHT)) return F(1);
-    return deg > 0 ? (F)(a.w / (double)deg) : F(0);
-}
-
-// w * s_j for the parity bit p of check j (1: s_j = -1): the sign bit of w flipped by p,
-// which is what the multiply by +-1 gives, bit for bit.
-__device__ __forceinline__ float rgdbf_term(float w, uint32_t p)
-{
-    return __uint_as_float(__float_as_uint(w) ^ (p << 31));
-}
-__device__ __forceinline__ double rgdbf_term(double w, uint32_t p)
-{
-    return __hiloint2double((int)((uint32_t)__double2hiint(w) ^ (p << 31)), __double2loint(w));
-}
+// The per-bit weight (rgdbf_weight, rgdbf_term, the LDS table of weights by degree) and the
+// state layout of a codeword are in rgdbf_shared.h, shared with rstat.hip.
 
 // ---------------------------------------------------------------------
 // Generic kernels: one workgroup per codeword, its state in LDS (rgdbf_lds) or in
 // a global slot (rgdbf_global), as gdbf_lds / gdbf_global.
 // ---------------------------------------------------------------------
-constexpr int kRgdbfWtab = 64;   // weights by degree kept in LDS; larger degrees divide in place
-
 template <typename F, int SRC>
 __device__ __forceinline__ void rgdbf_codeword(const RgdbfArgs &a, const DevGraph &g, int b, F *yq, F *theta,
                                                int16_t *dsum, int8_t *d, int8_t *r8, int8_t *s, int *red,
@@ -187,30 +169,6 @@ __device__ __forceinline__ void rgdbf_codeword(const RgdbfArgs &a, const DevGrap
     __syncthreads();
 }
 
-// Byte offsets of one codeword's state: yq[N] | theta[N] | dsum[N] (int16) | d[N] | r[N] | s[M].
-struct RgdbfLayout {
-    size_t theta, dsum, d, r, s, total;
-};
-static RgdbfLayout rgdbf_layout(int N, int M, size_t fsz)
-{
-    RgdbfLayout L;
-    auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
-    L.theta = al(fsz * N);
-    L.dsum = L.theta + al(fsz * N);
-    L.d = L.dsum + al(2 * (size_t)N);
-    L.r = L.d + al((size_t)N);
-    L.s = L.r + al((size_t)N);
-    L.total = L.s + al((size_t)M);
-    return L;
-}
-
-template <typename F>
-__device__ __forceinline__ void rgdbf_fill_wtab(const RgdbfArgs &a, F *wtab)
-{
-    for (int k = threadIdx.x; k < kRgdbfWtab; k += blockDim.x) wtab[k] = rgdbf_weight<F>(a, k);
-    __syncthreads();
-}
-
 template <typename F, int SRC>
 __global__ __launch_bounds__(256) void k_rgdbf_lds(RgdbfArgs a, DevGraph g, RgdbfLayout L)
 {
@@ -258,19 +216,7 @@ __global__ __launch_bounds__(1024) void k_rgdbf_global(RgdbfArgs a, DevGraph g, 
 // store and one barrier; the early-stop flag alternates on the perturbation row
 // ph * T + it, which keeps alternating across a restart for odd and even T.
 // ---------------------------------------------------------------------
-struct RgdbfRowsLayout {
-    int np, poff, floff, total;
-};
-static RgdbfRowsLayout rgdbf_rows_layout(int N, int M)
-{
-    RgdbfRowsLayout L;
-    L.np = ((N + 3) & ~3) + 4;                 // d < 0 flags [0..N) + pad; the last word: dummy bits (0)
-    L.poff = (L.np + 7) & ~7;
-    L.floff = L.poff + ((M + 1 + 7) & ~7);     // parity bytes [0..M), [M]: the dummy check
-    L.total = L.floff + 16;                    // flags[2] (+ pad)
-    return L;
-}
-
+// RgdbfRowsLayout / rgdbf_rows_layout: rgdbf_shared.h.
 // Every instance is bounded to 4 waves per SIMD (128 VGPRs): at gdbf_rows' 6 the fp32
 // 512-thread instances spilled 16 to 128 bytes per lane (r, the weights and the degrees
 // are registers gdbf_rows does not hold).
@@ -530,8 +476,7 @@ LDPC_CHECK_TU(rgdbf)
 RgdbfChoice rgdbf_choose(const DevGraph &g, bool f64, int maxdv, int maxdc)
 {
     RgdbfChoice ch;
-    if (g.N >= 1 && g.N <= 4 * 1024 && g.M <= 2 * 1024 && maxdc <= 8 && maxdv <= 12 &&
-        opt(LDPC_OPT_GDBF_KERNEL) != 1) {
+    if (rgdbf_rows_fits(g.N, g.M, maxdv, maxdc) && opt(LDPC_OPT_GDBF_KERNEL) != 1) {
         ch.name = "rgdbf_rows";
         ch.threads = g.N <= 4 * 512 && g.M <= 2 * 512 ? 512 : 1024;
         ch.dvm = maxdv <= 4 ? 4 : 12;

@@ -157,6 +157,43 @@ class RgdbfConfig:
                          self.lambda_, self.alpha, self.noise_scale, self.ymax)
 
 
+class _RstatCfg(C.Structure):
+    _fields_ = [("flags", C.c_int32), ("precision", C.c_int32), ("T", C.c_int32), ("attempts", C.c_int32),
+                ("windowsize", C.c_int32), ("first_attempt", C.c_int32), ("theta", C.c_double),
+                ("lambda_", C.c_double), ("alpha", C.c_double), ("noise_scale", C.c_double), ("ymax", C.c_double)]
+
+
+class _RstatTrace(C.Structure):
+    _fields_ = [("err_trace", C.c_void_p), ("unsat_trace", C.c_void_p), ("d_trace", C.c_void_p),
+                ("s_trace", C.c_void_p)]
+
+
+ATTEMPT_DTYPE = np.dtype([("bit_err", np.int32), ("iters", np.int32), ("syndrome_fail", np.int32),
+                          ("smoothing_used", np.int32)])
+
+
+@dataclass
+class RstatConfig:
+    """Every attempt of every frame (src/newstat.cpp = redecodeStatistics, src/replayGDBF.cpp):
+    `attempts` single-phase decodes of T iterations per frame from the same channel samples,
+    all of them run; attempt indices start at first_attempt. flags a subset of RGDBF_FLAGS."""
+    flags: int = RGDBF_FLAGS
+    T: int = 100
+    attempts: int = 5
+    first_attempt: int = 0
+    theta: float = -0.6
+    lambda_: float = 0.99
+    alpha: float = 0.96
+    noise_scale: float = 0.75
+    ymax: float = 2.5
+    windowsize: int = 16
+    precision: int = 1   # F64, the reference's double; F32 = 0 opt-in
+
+    def _c(self) -> _RstatCfg:
+        return _RstatCfg(self.flags, self.precision, self.T, self.attempts, self.windowsize, self.first_attempt,
+                         self.theta, self.lambda_, self.alpha, self.noise_scale, self.ymax)
+
+
 class _HwGdbfCfg(C.Structure):
     _fields_ = [("precision", C.c_int32), ("T", C.c_int32), ("maxphase", C.c_int32), ("nq", C.c_int32),
                 ("qlen", C.c_int32), ("reserved", C.c_int32), ("w", C.c_double), ("ymax", C.c_double),
@@ -305,6 +342,15 @@ def lib():
         "ldpc_rgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
                                  i32),
         "ldpc_rgdbf_kernel_info": ([vp, C.POINTER(_RgdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
+        "ldpc_rstat_decode_batch": ([vp, vp, vp, i32, C.POINTER(_RstatCfg), vp, vp, C.POINTER(_RstatTrace), vp, vp,
+                                     C.POINTER(Counts)], i32),
+        "ldpc_rstat_sim_launch": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, C.POINTER(_RstatTrace),
+                                   vp], i32),
+        "ldpc_rstat_sim_batch": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, C.POINTER(_RstatTrace),
+                                  vp, C.POINTER(Counts)], i32),
+        "ldpc_rstat_sim_trace": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, vp, vp,
+                                  C.POINTER(_RstatTrace), vp, vp, C.POINTER(Counts)], i32),
+        "ldpc_rstat_kernel_info": ([vp, C.POINTER(_RstatCfg), i32, C.c_char_p, i32, C.POINTER(i32)], i32),
         "ldpc_hwgdbf_decode_batch": ([vp, vp, vp, vp, i32, C.POINTER(_HwGdbfCfg), vp, vp, vp, vp, C.POINTER(Counts)],
                                      i32),
         "ldpc_hwgdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp], i32),
@@ -349,6 +395,8 @@ EXPORTED = ["ldpc_abi_version", "ldpc_f64_nms_fast_division", "ldpc_bp_math_prob
             "ldpc_ctx_row_sched_info", "ldpc_ctx_set_option", "ldpc_ctx_get_option", "ldpc_nb_ctx_set_option",
             "ldpc_gdbf_decode_batch", "ldpc_gdbf_sim_launch", "ldpc_gdbf_sim_batch", "ldpc_gdbf_kernel_info",
             "ldpc_rgdbf_decode_batch", "ldpc_rgdbf_sim_launch", "ldpc_rgdbf_sim_batch", "ldpc_rgdbf_kernel_info",
+            "ldpc_rstat_decode_batch", "ldpc_rstat_sim_launch", "ldpc_rstat_sim_batch", "ldpc_rstat_sim_trace",
+            "ldpc_rstat_kernel_info",
             "ldpc_hwgdbf_decode_batch", "ldpc_hwgdbf_sim_launch", "ldpc_hwgdbf_sim_batch", "ldpc_hwgdbf_sim_trace",
             "ldpc_hwgdbf_kernel_info",
             "ldpc_nb_graph_create", "ldpc_nb_graph_load_alist", "ldpc_nb_graph_info", "ldpc_nb_graph_destroy",
@@ -645,6 +693,87 @@ class Context:
         name = C.create_string_buffer(32)
         lds = C.c_int()
         _check(lib().ldpc_rgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
+        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+
+    # ---- every attempt of every frame (src/newstat.cpp, src/replayGDBF.cpp) ----
+    def _rstat_trace(self, batch: int, cfg: RstatConfig, want: bool):
+        """(the ldpc_rstat_trace argument or None, the dict of its numpy arrays or None)."""
+        if not want:
+            return None, None
+        shape = (batch, cfg.attempts, cfg.T)
+        tr = {"err_trace": np.empty(shape, dtype=np.int32), "unsat_trace": np.empty(shape, dtype=np.int32),
+              "d_trace": np.empty(shape + (self.graph.N,), dtype=np.int8),
+              "s_trace": np.empty(shape + (self.graph.M,), dtype=np.int8)}
+        return C.byref(_RstatTrace(*(tr[k].ctypes.data for k, _ in _RstatTrace._fields_))), tr
+
+    def rstat_decode(self, y, pert, cfg: RstatConfig, c=None, want_trace: bool = False):
+        """Decode raw channel samples y[batch, N] cfg.attempts times each with perturbations
+        pert[batch, attempts, T, N] (None without GDBF_NOISE). Returns (attempts, d, frames,
+        Counts, trace): attempts[batch, attempts] of ATTEMPT_DTYPE; d, frames' bit_err and
+        syndrome_fail are the last attempt's and iters the sum over the attempts; trace is a
+        dict of err_trace, unsat_trace, d_trace, s_trace (None unless want_trace)."""
+        N = self.graph.N
+        want = np.float64 if cfg.precision == F64 else np.float32
+        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
+        batch = y.shape[0]
+        if pert is not None:
+            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.attempts, cfg.T, N)
+        if c is not None:
+            c = np.ascontiguousarray(c, dtype=np.int8)
+        att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
+        d = np.empty((batch, N), dtype=np.int8)
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        targ, tr = self._rstat_trace(batch, cfg, want_trace)
+        _check(lib().ldpc_rstat_decode_batch(self._h, _ptr(y), _ptr(pert), batch, C.byref(cfg._c()), _ptr(c),
+                                             _ptr(att), targ, _ptr(d), _ptr(fr), C.byref(cnt)))
+        return att, d, fr, cnt, tr
+
+    def rstat_sim_launch(self, ebn0_db: float, R: float, cfg: RstatConfig, seed: int, stream_id: int, first_cw: int,
+                         batch: int, attempts_dev=None, frames_dev=None, trace_dev: Optional[dict] = None):
+        """Asynchronous; every output is a device tensor or None. trace_dev: a dict with any of
+        err_trace, unsat_trace [batch, attempts, T] int32 and d_trace [.., N], s_trace [.., M] int8."""
+        targ = None
+        if trace_dev:
+            unknown = set(trace_dev) - {k for k, _ in _RstatTrace._fields_}
+            if unknown:
+                raise KeyError(f"unknown trace {sorted(unknown)}")
+            targ = C.byref(_RstatTrace(*(_ptr(trace_dev.get(k)) for k, _ in _RstatTrace._fields_)))
+        _check(lib().ldpc_rstat_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                           _ptr(attempts_dev), targ, _ptr(frames_dev)))
+
+    def rstat_sim(self, ebn0_db: float, R: float, cfg: RstatConfig, seed: int, stream_id: int, first_cw: int,
+                  batch: int, want_trace: bool = False):
+        """Fused Monte-Carlo of batch frames x cfg.attempts attempts: (attempts, frames, Counts, trace)."""
+        att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        targ, tr = self._rstat_trace(batch, cfg, want_trace)
+        _check(lib().ldpc_rstat_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                          _ptr(att), targ, _ptr(fr), C.byref(cnt)))
+        return att, fr, cnt, tr
+
+    def rstat_sim_trace(self, ebn0_db: float, R: float, cfg: RstatConfig, seed: int, stream_id: int, first_cw: int,
+                        batch: int, want_trace: bool = False):
+        """rstat_sim that also returns the samples drawn: (y, pert, attempts, d, frames, Counts,
+        trace) with pert[batch, attempts, T, N]; rows that were not drawn are zero."""
+        N = self.graph.N
+        want = np.float64 if cfg.precision == F64 else np.float32
+        y = np.empty((batch, N), dtype=want)
+        pert = np.empty((batch, cfg.attempts, cfg.T, N), dtype=want)
+        att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
+        d = np.empty((batch, N), dtype=np.int8)
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        targ, tr = self._rstat_trace(batch, cfg, want_trace)
+        _check(lib().ldpc_rstat_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
+                                          _ptr(y), _ptr(pert), _ptr(att), targ, _ptr(d), _ptr(fr), C.byref(cnt)))
+        return y, pert, att, d, fr, cnt, tr
+
+    def rstat_kernel_info(self, cfg: RstatConfig, with_trace: bool = False) -> dict:
+        name = C.create_string_buffer(32)
+        lds = C.c_int()
+        _check(lib().ldpc_rstat_kernel_info(self._h, C.byref(cfg._c()), int(with_trace), name, 32, C.byref(lds)))
         return {"kernel": name.value.decode(), "lds_bytes": lds.value}
 
     # ---- fixed-point NGDBF hardware model (src/NGDBFhw.cpp) ----

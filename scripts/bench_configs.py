@@ -38,7 +38,9 @@ rsmngdbf_* lines; c4_rgdbf_single_* is rgdbf_rows doing gdbf_rows' work on confi
 weight 1, for the A/B of the two kernels), src/NGDBFhw.cpp:280-373 and :546-593 (the hwgdbf_*
 lines at the reference's constants and its R = 0.8413; *_wg forces the workgroup-per-codeword
 instance for the A/B of the two kernel shapes; where that is the library's own choice, the
-wavefront shape is measured with --lib on `make hwgdbfvariant VFLAGS=-DLDPC_HWGDBF_FORCE_WAVE`).
+wavefront shape is measured with --lib on `make hwgdbfvariant VFLAGS=-DLDPC_HWGDBF_FORCE_WAVE`),
+src/newstat.cpp:305-429 (the rstat_* lines: 200 frames x 100 attempts as scripts/redecode_statistics_802.3.sh
+runs them; *_wg forces the workgroup-per-attempt kernel).
 """
 import argparse
 import csv
@@ -126,6 +128,21 @@ for _code, _tag, _snr in (("802_3_H.alist", "802_3", 4.0), ("PEGReg504x1008.alis
                 what=f"NGDBFhw on {_tag}, T<=600, {_prec} front end, "
                      f"{'hwgdbf_wg forced' if _k else 'the kernel the library chooses'}")
 
+# every attempt of every frame (src/newstat.cpp, src/replayGDBF.cpp): NF 200 frames x NR 100 attempts, the shape of
+# the reference's scripts/redecode_statistics_802.3.sh (802.3an at 4.0 dB, R 0.8125, T 1000, theta -0.525, noiseScale
+# 0.92, lambda 1, alpha 0.5, window 64) and N=1944 at 4.0 dB with the golden run's settings; `batch` counts frames
+for _code, _tag, _rate, _kw in (
+        ("802_3_H.alist", "802_3", 0.8125, dict(T=1000, theta=-0.525, lambda_=1.0, alpha=0.5, noise_scale=0.92, windowsize=64)),
+        ("80211n_1944_r12.alist", "1944", 0.5, dict(T=100, theta=-0.6, lambda_=0.99, alpha=1.5, noise_scale=0.75, windowsize=16))):
+    for _prec in ("f32", "f64"):
+        for _k, _kname in ((0, ""), (1, "_wg")):
+            CONFIGS[f"rstat_{_tag}_{_prec}{_kname}"] = dict(
+                kind="rstat", code=_code, prec=_prec, T=_kw["T"], batch=200, attempts=100, snr=4.0, rate=_rate, cfg=_kw,
+                gdbf_kernel=_k,
+                what=f"redecodeStatistics on {_tag}: 200 frames x 100 attempts, T<={_kw['T']}, {_prec}, "
+                     f"{'rstat_wg forced' if _k else 'the kernel the library chooses'}; value counts attempts x N bits, "
+                     f"avg_iters is per frame (summed over its attempts)")
+
 PMC_PASSES = [
     "SQ_WAVES SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY "
     "GRBM_GUI_ACTIVE",
@@ -182,6 +199,12 @@ class Workload:
                                           precision=prec)
             self.launch_fn = self.ctx.rgdbf_sim_launch
             self.kernel = self.ctx.rgdbf_kernel_info(self.cfg)["kernel"]
+        elif c["kind"] == "rstat":
+            self.cfg = native.RstatConfig(attempts=c["attempts"], ymax=2.5, precision=prec, **c["cfg"])
+            self.ctx.set_option("gdbf_kernel", c["gdbf_kernel"])
+            self.bits = self.g.N * c["attempts"]
+            self.launch_fn = self.ctx.rstat_sim_launch
+            self.kernel = self.ctx.rstat_kernel_info(self.cfg)["kernel"]
         elif c["kind"] == "hwgdbf":
             self.cfg = native.HwGdbfConfig(T=c["T"], precision=prec)
             self.ctx.set_option("gdbf_kernel", c["gdbf_kernel"])
