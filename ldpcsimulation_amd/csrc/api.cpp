@@ -29,7 +29,7 @@
 #include "kernels.h"
 #include "host_rt.h"
 
-using namespace ldpc;   // host_rt.h: set_err, HIP_TRY, DevBuf, OutStage, stage_in, CtxCore, Blob
+using namespace ldpc;   // host_rt.h: set_err, HIP_TRY, DevBuf, CtxCore, Blob and the call skeleton
 
 static thread_local std::string g_last_error;
 
@@ -195,6 +195,61 @@ static hipError_t upload_layer_sched(const ldpc::LayerSchedule &lh, DevBuf &buf,
           section<uint8_t>(buf, o_rd), section<int32_t>(buf, o_pb)};
     for (int L = 0; L < ls.nlayers; ++L) ls.max_layer = std::max(ls.max_layer, lh.lptr[L + 1] - lh.lptr[L]);
     return hipSuccess;
+}
+
+// ----------------------------------------------------------------- the binary families' shared steps
+static const char kFramesDev[] = "frames_dev must be a device pointer";
+
+// The given samples of a decode call, in the order they are copied: y, the family's second
+// input of `extra_elems` samples (pert / q; null: none) and the codewords sent.
+template <class Args>
+static int stage_given(SyncCall &s, ldpc_ctx *c, Args &a, bool f64, const void *y, const void *extra, size_t extra_elems,
+                       const void **extra_dev, const int8_t *cw)
+{
+    const size_t fsz = f64 ? 8 : 4, nb = (size_t)a.batch * c->g->N;
+    a.src = ldpc::SRC_GIVEN;
+    RC_TRY(s.in(y, nb * fsz, c->y_stage, a.y));
+    if (extra) RC_TRY(s.in(extra, extra_elems * fsz, c->p_stage, *extra_dev));
+    return s.in(cw, nb, c->c_stage, a.c);
+}
+
+// After the checks: the synchronous form of a launch whose only output is the frame records.
+template <class Run>
+static int sim_batch_frames(ldpc_ctx *c, int batch, ldpc_frame_result *frames, ldpc_counts *accum, Run run)
+{
+    RC_TRY(c->enter());
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    ldpc_frame_result *w;
+    RC_TRY(s.out(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch, w));
+    RC_TRY(run(w));
+    return s.finish(accum);
+}
+
+// The decisions and the frame records, host or device.
+template <class Args>
+static int bind_decisions(SyncCall &s, ldpc_ctx *c, Args &a, int8_t *d_out, ldpc_frame_result *frames)
+{
+    RC_TRY(s.out(d_out, c->d_stage, (size_t)a.batch * c->g->N, a.d_out));
+    return s.out(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)a.batch, a.frame_res);
+}
+
+// What ldpc_rgdbf_cfg and ldpc_rstat_cfg have in common: the flags, the per-bit syndrome
+// weight and no quantiser.
+template <class Args, class Cfg> static void redecode_fill(Args &a, ldpc_ctx *c, const Cfg *cfg, int batch)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.flags = cfg->flags;
+    a.windowsize = cfg->windowsize;
+    a.theta0 = cfg->theta;
+    a.lambda = cfg->lambda;
+    // RNGDBF.cpp:566 and newstat.cpp symNodeUpdates, alpha*Ymax/dv left to right: the kernels divide
+    a.w = cfg->alpha * cfg->ymax;
+    a.ymax = cfg->ymax;
+    a.qmax = 1.0;
+    fill_accounting(a, *c);
 }
 
 extern "C" {
@@ -616,32 +671,19 @@ int ldpc_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_decoder_
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
     RC_TRY(check_cfg(c, cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    RC_TRY(c->enter());
+    RC_TRY(check_batch(*c, batch));
     if (cfg->variant == LDPC_BP && !(cfg->n0 > 0)) return set_err(LDPC_ERR_INVALID, "BP needs cfg->n0 > 0");
+    RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
-    const int N = c->g->N;
-    const size_t ybytes = (size_t)batch * N * (f64 ? 8 : 4);
-    const size_t nbytes = (size_t)batch * N;
-
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, batch);
-    a.src = ldpc::SRC_GIVEN;
     RC_TRY(nms_setup(c, cfg, a));
-    HIP_TRY(stage_in(y, ybytes, c->y_stage, c->stream, a.y));
-    HIP_TRY(stage_in(cw, nbytes, c->c_stage, c->stream, a.c));
-    OutStage d, w;
-    HIP_TRY(d.bind(d_out, c->d_stage, nbytes));
-    HIP_TRY(w.bind(frame_weights, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    a.d_out = (int8_t *)d.dev;
-    a.frame_res = (int4 *)w.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, nullptr, 0, nullptr, cw));
+    RC_TRY(bind_decisions(s, c, a, d_out, frame_weights));
+    RC_TRY(s.snapshot());
     RC_TRY(run_kernel(c, a, f64, cfg->schedule));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
 // ----------------------------------------------------------------- Monte-Carlo
@@ -664,28 +706,16 @@ int ldpc_sim_set_codewords(ldpc_ctx *c, const uint8_t *bits, int rows)
     return LDPC_OK;
 }
 
-static int sim_launch_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
-                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev,
-                           void *y_out_dev, int8_t *d_out_dev)
+// After the checks and enter(); y_out_dev / d_out_dev: device pointers or null.
+static int sim_run(ldpc_ctx *c, const SimCall &q, const ldpc_decoder_cfg *cfg, ldpc_frame_result *frames_dev,
+                   void *y_out_dev, int8_t *d_out_dev)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(check_cfg(c, cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    RC_TRY(c->enter());
     ldpc::DecodeArgs a;
-    fill_common(a, c, cfg, batch);
-    a.src = ldpc::SRC_PHILOX;
+    fill_common(a, c, cfg, q.batch);
     RC_TRY(nms_setup(c, cfg, a));
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // :146
-    a.sigma = std::sqrt(N0 / 2.0);                            // :147
-    if (cfg->variant == LDPC_BP) a.n0 = N0;                   // 4*y/N0 (decodeBP.cpp:104,188)
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
-    a.cw_rows = c->cw_rows;
+    const SimPoint pt = fill_sim(a, *c, q);      // :146-147
+    fill_cw_table(a, *c);
+    if (cfg->variant == LDPC_BP) a.n0 = pt.N0;   // 4*y/N0 (decodeBP.cpp:104,188)
     a.frame_res = (int4 *)frames_dev;
     a.y_out = y_out_dev;
     a.d_out = d_out_dev;
@@ -695,9 +725,11 @@ static int sim_launch_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_dec
 int ldpc_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
                     uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev))
-        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
-    return sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev, nullptr, nullptr);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return check_cfg(c, cfg); }, q, false));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    return sim_run(c, q, cfg, frames_dev, nullptr, nullptr);
 }
 
 int ldpc_ctx_read_counts(ldpc_ctx *c, ldpc_counts *out, int reset)
@@ -718,42 +750,30 @@ int ldpc_ctx_read_histogram(ldpc_ctx *c, int64_t *out, int reset)
 }
 
 // Synchronous sim with optional host-or-device outputs (staged when host).
-static int sim_sync_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
-                         uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *d_out,
-                         ldpc_frame_result *frames, ldpc_counts *accum)
+int ldpc_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
+                   uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *d_out,
+                   ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(check_cfg(c, cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return check_cfg(c, cfg); }, q, false));
     RC_TRY(c->enter());
     const size_t nb = (size_t)batch * c->g->N;
-    const size_t ybytes = nb * (cfg->precision == LDPC_F64 ? 8 : 4);
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
-    OutStage w, y, d;
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    HIP_TRY(y.bind(y_out, c->y_stage, ybytes));
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    RC_TRY(sim_launch_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev, y.dev,
-                           (int8_t *)d.dev));
-    HIP_TRY(w.fetch(c->stream));
-    HIP_TRY(y.fetch(c->stream));
-    HIP_TRY(d.fetch(c->stream));
-    return c->counts_since(before, accum);
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    ldpc_frame_result *w;
+    void *y;
+    int8_t *d;
+    RC_TRY(s.out(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch, w));
+    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), y));
+    RC_TRY(s.out(d_out, c->d_stage, nb, d));
+    RC_TRY(sim_run(c, q, cfg, w, y, d));
+    return s.finish(accum);
 }
 
 int ldpc_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
                    uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    return sim_sync_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, frames, accum);
-}
-
-int ldpc_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_decoder_cfg *cfg, uint64_t seed,
-                   uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *d_out,
-                   ldpc_frame_result *frames, ldpc_counts *accum)
-{
-    return sim_sync_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, y_out, d_out, frames, accum);
+    return ldpc_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, frames, accum);
 }
 
 int ldpc_ctx_last_kernel_ms(ldpc_ctx *c, float *ms)
@@ -765,8 +785,8 @@ int ldpc_ctx_last_kernel_ms(ldpc_ctx *c, float *ms)
 static int info_plan(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, ldpc::LaunchPlan &p)
 {
     if (!c || !cfg) return set_err(LDPC_ERR_INVALID, "null argument");
-    RC_TRY(c->enter());
     RC_TRY(check_cfg(c, cfg));
+    RC_TRY(c->enter());
     ldpc::DecodeArgs a;
     fill_common(a, c, cfg, 1);
     RC_TRY(nms_setup(c, cfg, a));   // fp32 NMS: whether the verified reciprocal (and so the fast kernels) applies
@@ -816,10 +836,8 @@ int ldpc_ctx_kernel_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, char *name, i
 {
     ldpc::LaunchPlan p;
     RC_TRY(info_plan(c, cfg, p));
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", p.name);
-    if (lds_bytes) *lds_bytes = p.lds_bytes;
     if (bpc) *bpc = p.blocks_per_cu;
-    return LDPC_OK;
+    return report_choice(p, name, name_len, lds_bytes);
 }
 
 
@@ -859,23 +877,16 @@ static void gdbf_fill(ldpc::GdbfArgs &a, ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, 
     a.qmax = std::pow(2, (cfg->nq - 1));                       // :490
     a.tswitch = cfg->tswitch;
     a.qsigma = cfg->qsigma;
-    a.counts = (unsigned long long *)c->counts.p;
-    a.hist = (unsigned long long *)c->hist.p;
-    a.ticket = c->ticket();
+    fill_accounting(a, *c);
 }
 
 static int gdbf_run(ldpc_ctx *c, const ldpc::GdbfArgs &a, bool f64)
 {
     const ldpc::OptScope os(c->opts);
     const ldpc::GdbfChoice ch = ldpc::gdbf_choose(c->dg, f64, a.flags, c->g->maxdv, c->g->maxdc);
-    int slots = 0;
-    if (ch.slot_bytes) {
-        slots = std::min(a.batch, 2 * c->num_cus);
-        HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
-    }
-    RC_TRY(c->begin_launch());
-    HIP_TRY(ldpc::gdbf_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
-    return c->end_launch();
+    return run_with_slots(*c, c->gscratch, ch, a.batch, 2 * c->num_cus, [&](void *scratch, int slots) {
+        return ldpc::gdbf_launch(c->dg, a, f64, ch, scratch, slots, c->num_cus, c->stream);
+    });
 }
 
 int ldpc_gdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_gdbf_cfg *cfg,
@@ -883,82 +894,52 @@ int ldpc_gdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int bat
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
     RC_TRY(gdbf_check_cfg(cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if ((cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB)) && !pert)
-        return set_err(LDPC_ERR_INVALID, "NOISE / QPROB need pert");
+    RC_TRY(check_batch(*c, batch));
+    const bool with_pert = cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB);
+    if (with_pert && !pert) return set_err(LDPC_ERR_INVALID, "NOISE / QPROB need pert");
     if ((cfg->flags & LDPC_GDBF_QPROB) && !(cfg->qsigma > 0)) return set_err(LDPC_ERR_INVALID, "QPROB needs qsigma > 0");
     RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
-    const int N = c->g->N;
-    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
     ldpc::GdbfArgs a;
     gdbf_fill(a, c, cfg, batch);
-    a.src = ldpc::SRC_GIVEN;
-    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
-    if (cfg->flags & (LDPC_GDBF_NOISE | LDPC_GDBF_QPROB))
-        HIP_TRY(stage_in(pert, nb * (size_t)cfg->T * fsz, c->p_stage, c->stream, a.pert));
-    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
-    OutStage d, w;
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    a.d_out = (int8_t *)d.dev;
-    a.frame_res = (int4 *)w.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, with_pert ? pert : nullptr, (size_t)batch * c->g->N * (size_t)cfg->T, &a.pert, cw));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
     RC_TRY(gdbf_run(c, a, f64));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
-static int gdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_cfg *cfg, uint64_t seed,
-                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+// After the checks and enter().
+static int gdbf_sim_run(ldpc_ctx *c, const SimCall &q, const ldpc_gdbf_cfg *cfg, ldpc_frame_result *frames_dev)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(gdbf_check_cfg(cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
-    RC_TRY(c->enter());
     ldpc::GdbfArgs a;
-    gdbf_fill(a, c, cfg, batch);
-    a.src = ldpc::SRC_PHILOX;
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // :175-176
-    a.sigma = std::sqrt(N0 / 2.0);
+    gdbf_fill(a, c, cfg, q.batch);
+    fill_sim(a, *c, q);                                       // :175-176
+    fill_cw_table(a, *c);
+    a.frame_res = (int4 *)frames_dev;
     a.noise_sigma = a.sigma * cfg->noise_scale;               // :296
     a.qsigma = a.noise_sigma;                                  // symNodeUpdates' sigma (:353, :563)
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
-    a.cw_rows = c->cw_rows;
-    a.frame_res = (int4 *)frames_dev;
     return gdbf_run(c, a, cfg->precision == LDPC_F64);
 }
 
 int ldpc_gdbf_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_cfg *cfg, uint64_t seed,
                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev))
-        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
-    return gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return gdbf_check_cfg(cfg); }, q, true));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    return gdbf_sim_run(c, q, cfg, frames_dev);
 }
 
 int ldpc_gdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_gdbf_cfg *cfg, uint64_t seed,
                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
                         ldpc_counts *accum)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(c->enter());
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
-    OutStage w;   // batch is checked by gdbf_sim_impl
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
-    RC_TRY(gdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, accum);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return gdbf_check_cfg(cfg); }, q, true));
+    return sim_batch_frames(c, batch, frames, accum, [&](ldpc_frame_result *w) { return gdbf_sim_run(c, q, cfg, w); });
 }
 
 int ldpc_gdbf_kernel_info(ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, char *name, int name_len, int *lds_bytes)
@@ -966,10 +947,8 @@ int ldpc_gdbf_kernel_info(ldpc_ctx *c, const ldpc_gdbf_cfg *cfg, char *name, int
     RC_TRY(gdbf_check_cfg(cfg));
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
-    const ldpc::GdbfChoice ch = ldpc::gdbf_choose(c->dg, cfg->precision == LDPC_F64, cfg->flags, c->g->maxdv, c->g->maxdc);
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
-    if (lds_bytes) *lds_bytes = ch.lds_bytes;
-    return LDPC_OK;
+    return report_choice(ldpc::gdbf_choose(c->dg, cfg->precision == LDPC_F64, cfg->flags, c->g->maxdv, c->g->maxdc), name,
+                         name_len, lds_bytes);
 }
 
 // ----------------------------------------------------------------- re-decoding NGDBF
@@ -995,34 +974,17 @@ static int rgdbf_check_cfg(const ldpc_rgdbf_cfg *cfg)
 
 static void rgdbf_fill(ldpc::RgdbfArgs &a, ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, int batch)
 {
-    std::memset((void *)&a, 0, sizeof a);
-    a.batch = batch;
-    a.T = cfg->T;
+    redecode_fill(a, c, cfg, batch);
     a.maxphase = cfg->maxphase;
-    a.flags = cfg->flags;
-    a.windowsize = cfg->windowsize;
-    a.theta0 = cfg->theta;
-    a.lambda = cfg->lambda;
-    a.w = cfg->alpha * cfg->ymax;   // RNGDBF.cpp:566, alpha*Ymax/dv left to right: the kernels divide
-    a.ymax = cfg->ymax;
-    a.qmax = 1.0;
-    a.counts = (unsigned long long *)c->counts.p;
-    a.hist = (unsigned long long *)c->hist.p;
-    a.ticket = c->ticket();
 }
 
 static int rgdbf_run(ldpc_ctx *c, const ldpc::RgdbfArgs &a, bool f64)
 {
     const ldpc::OptScope os(c->opts);
     const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, f64, c->g->maxdv, c->g->maxdc);
-    int slots = 0;
-    if (ch.slot_bytes) {
-        slots = std::min(a.batch, 2 * c->num_cus);
-        HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
-    }
-    RC_TRY(c->begin_launch());
-    HIP_TRY(ldpc::rgdbf_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
-    return c->end_launch();
+    return run_with_slots(*c, c->gscratch, ch, a.batch, 2 * c->num_cus, [&](void *scratch, int slots) {
+        return ldpc::rgdbf_launch(c->dg, a, f64, ch, scratch, slots, c->num_cus, c->stream);
+    });
 }
 
 int ldpc_rgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_rgdbf_cfg *cfg,
@@ -1030,80 +992,51 @@ int ldpc_rgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int ba
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
     RC_TRY(rgdbf_check_cfg(cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if ((cfg->flags & LDPC_GDBF_NOISE) && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
+    RC_TRY(check_batch(*c, batch));
+    const bool noise = cfg->flags & LDPC_GDBF_NOISE;
+    if (noise && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
     RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
-    const int N = c->g->N;
-    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
     ldpc::RgdbfArgs a;
     rgdbf_fill(a, c, cfg, batch);
-    a.src = ldpc::SRC_GIVEN;
-    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
-    if (cfg->flags & LDPC_GDBF_NOISE)
-        HIP_TRY(stage_in(pert, nb * (size_t)cfg->T * (size_t)cfg->maxphase * fsz, c->p_stage, c->stream, a.pert));
-    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
-    OutStage d, w;
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    a.d_out = (int8_t *)d.dev;
-    a.frame_res = (int4 *)w.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, noise ? pert : nullptr,
+                       (size_t)batch * c->g->N * (size_t)cfg->T * (size_t)cfg->maxphase, &a.pert, cw));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
     RC_TRY(rgdbf_run(c, a, f64));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
-static int rgdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
-                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+// After the checks and enter().
+static int rgdbf_sim_run(ldpc_ctx *c, const SimCall &q, const ldpc_rgdbf_cfg *cfg, ldpc_frame_result *frames_dev)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(rgdbf_check_cfg(cfg));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
-    RC_TRY(c->enter());
     ldpc::RgdbfArgs a;
-    rgdbf_fill(a, c, cfg, batch);
-    a.src = ldpc::SRC_PHILOX;
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // RNGDBF.cpp:167-168
-    a.sigma = std::sqrt(N0 / 2.0);
-    a.noise_sigma = a.sigma * cfg->noise_scale;               // :308
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
-    a.cw_rows = c->cw_rows;
+    rgdbf_fill(a, c, cfg, q.batch);
+    fill_sim(a, *c, q);                                       // RNGDBF.cpp:167-168
+    fill_cw_table(a, *c);
     a.frame_res = (int4 *)frames_dev;
+    a.noise_sigma = a.sigma * cfg->noise_scale;               // :308
     return rgdbf_run(c, a, cfg->precision == LDPC_F64);
 }
 
 int ldpc_rgdbf_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev))
-        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
-    return rgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return rgdbf_check_cfg(cfg); }, q, true));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    return rgdbf_sim_run(c, q, cfg, frames_dev);
 }
 
 int ldpc_rgdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rgdbf_cfg *cfg, uint64_t seed,
                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
                          ldpc_counts *accum)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(rgdbf_check_cfg(cfg));
-    RC_TRY(c->enter());
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
-    OutStage w;   // batch is checked by rgdbf_sim_impl
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)std::max(batch, 1)));
-    RC_TRY(rgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)w.dev));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, accum);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_sim(c, [&] { return rgdbf_check_cfg(cfg); }, q, true));
+    return sim_batch_frames(c, batch, frames, accum, [&](ldpc_frame_result *w) { return rgdbf_sim_run(c, q, cfg, w); });
 }
 
 int ldpc_rgdbf_kernel_info(ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes)
@@ -1111,10 +1044,8 @@ int ldpc_rgdbf_kernel_info(ldpc_ctx *c, const ldpc_rgdbf_cfg *cfg, char *name, i
     RC_TRY(rgdbf_check_cfg(cfg));
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
-    const ldpc::RgdbfChoice ch = ldpc::rgdbf_choose(c->dg, cfg->precision == LDPC_F64, c->g->maxdv, c->g->maxdc);
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
-    if (lds_bytes) *lds_bytes = ch.lds_bytes;
-    return LDPC_OK;
+    return report_choice(ldpc::rgdbf_choose(c->dg, cfg->precision == LDPC_F64, c->g->maxdv, c->g->maxdc), name, name_len,
+                         lds_bytes);
 }
 
 // ----------------------------------------------------------------- every attempt of every frame
@@ -1144,71 +1075,60 @@ static int rstat_check_cfg(const ldpc_rstat_cfg *cfg)
 
 static int rstat_check_batch(ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int batch)
 {
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    RC_TRY(check_batch(*c, batch));
     if ((int64_t)batch * cfg->attempts > INT32_MAX)
         return set_err(LDPC_ERR_INVALID, "batch * attempts must be <= 2^31 - 1");
     return LDPC_OK;
 }
 
-// The outputs of a launch the caller may hold on the host or on the device.
-struct RstatOuts {
-    OutStage att, tr[4];
-};
-
-// Fills the decoder's part of `a`, binds attempts_out and the traces (device_only: an
-// asynchronous launch takes device pointers only) and puts the "not run" values into the traces.
-static int rstat_fill(ldpc::RstatArgs &a, RstatOuts &o, ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int batch,
-                      ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace, bool device_only)
+// The refusals of the ldpc_rstat_sim_* calls that need no device.
+static int rstat_check_sim(ldpc_ctx *c, const ldpc_rstat_cfg *cfg, const SimCall &q)
 {
-    std::memset((void *)&a, 0, sizeof a);
-    a.batch = batch;
-    a.T = cfg->T;
-    a.attempts = cfg->attempts;
-    a.first_attempt = cfg->first_attempt;
-    a.flags = cfg->flags;
-    a.windowsize = cfg->windowsize;
-    a.theta0 = cfg->theta;
-    a.lambda = cfg->lambda;
-    a.w = cfg->alpha * cfg->ymax;   // newstat.cpp symNodeUpdates, alpha*Ymax/dv left to right: the kernels divide
-    a.ymax = cfg->ymax;
-    a.qmax = 1.0;
-    a.counts = (unsigned long long *)c->counts.p;
-    a.hist = (unsigned long long *)c->hist.p;
-    a.ticket = c->ticket();
-    const size_t items = (size_t)batch * cfg->attempts, rows = items * (size_t)cfg->T;
-    void *const tp[4] = {trace ? trace->err_trace : nullptr, trace ? trace->unsat_trace : nullptr,
-                         trace ? trace->d_trace : nullptr, trace ? trace->s_trace : nullptr};
-    if (device_only) {
-        if (attempts_out && !is_device_ptr(attempts_out))
-            return set_err(LDPC_ERR_INVALID, "attempts_out must be a device pointer");
-        for (void *p : tp)
-            if (p && !is_device_ptr(p)) return set_err(LDPC_ERR_INVALID, "the traces must be device pointers");
-    }
-    HIP_TRY(o.att.bind(attempts_out, c->rs_att_stage, sizeof(ldpc_attempt_result) * items));
-    if (!o.att.dev) {
-        HIP_TRY(c->rs_att_stage.ensure(sizeof(ldpc_attempt_result) * items));
-        o.att.dev = c->rs_att_stage.p;
-    }
-    a.attempt_res = (int4 *)o.att.dev;
-    HIP_TRY(c->rs_unc.ensure(sizeof(int) * (size_t)batch));
-    a.frame_unc = (int *)c->rs_unc.p;
-    const size_t tb[4] = {rows * 4, rows * 4, rows * (size_t)c->g->N, rows * (size_t)c->g->M};
-    for (int k = 0; k < 4; ++k) {
-        HIP_TRY(o.tr[k].bind(tp[k], c->rs_tr_stage[k], tb[k]));
-        if (o.tr[k].dev) HIP_TRY(hipMemsetAsync(o.tr[k].dev, k < 2 ? 0xFF : 0, tb[k], c->stream));   // -1 / 0: not run
-    }
-    a.err_trace = (int32_t *)o.tr[0].dev;
-    a.unsat_trace = (int32_t *)o.tr[1].dev;
-    a.d_trace = (int8_t *)o.tr[2].dev;
-    a.s_trace = (int8_t *)o.tr[3].dev;
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(rstat_check_cfg(cfg));
+    RC_TRY(rstat_check_batch(c, cfg, q.batch));
+    RC_TRY(check_sim_point(q, true));
+    // the attempt index takes the high word of the frame number in the Philox counter
+    if (q.first_cw > (1ull << 32) - (uint64_t)q.batch)
+        return set_err(LDPC_ERR_INVALID, "first_cw + batch must be <= 2^32");
     return LDPC_OK;
 }
 
-static int rstat_fetch(ldpc_ctx *c, const RstatOuts &o)
+static void rstat_fill(ldpc::RstatArgs &a, ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int batch)
 {
-    HIP_TRY(o.att.fetch(c->stream));
-    for (int k = 0; k < 4; ++k) HIP_TRY(o.tr[k].fetch(c->stream));
+    redecode_fill(a, c, cfg, batch);
+    a.attempts = cfg->attempts;
+    a.first_attempt = cfg->first_attempt;
+}
+
+static void rstat_traces(const ldpc_rstat_trace *trace, void *tp[4])
+{
+    tp[0] = trace ? trace->err_trace : nullptr;
+    tp[1] = trace ? trace->unsat_trace : nullptr;
+    tp[2] = trace ? trace->d_trace : nullptr;
+    tp[3] = trace ? trace->s_trace : nullptr;
+}
+
+// Binds attempts_out (the kernels write it whether or not the caller wants it) and the
+// traces, and puts the "not run" values into the traces.
+static int rstat_outs(SyncCall &s, ldpc_ctx *c, ldpc::RstatArgs &a, ldpc_attempt_result *attempts_out,
+                      const ldpc_rstat_trace *trace)
+{
+    const size_t items = (size_t)a.batch * a.attempts, rows = items * (size_t)a.T;
+    RC_TRY(s.out(attempts_out, c->rs_att_stage, sizeof(ldpc_attempt_result) * items, a.attempt_res, true));
+    HIP_TRY(c->rs_unc.ensure(sizeof(int) * (size_t)a.batch));
+    a.frame_unc = (int *)c->rs_unc.p;
+    const size_t tb[4] = {rows * 4, rows * 4, rows * (size_t)c->g->N, rows * (size_t)c->g->M};
+    void *tp[4], *dev[4];
+    rstat_traces(trace, tp);
+    for (int k = 0; k < 4; ++k) {
+        RC_TRY(s.out(tp[k], c->rs_tr_stage[k], tb[k], dev[k]));
+        if (dev[k]) HIP_TRY(hipMemsetAsync(dev[k], k < 2 ? 0xFF : 0, tb[k], c->stream));   // -1 / 0: not run
+    }
+    a.err_trace = (int32_t *)dev[0];
+    a.unsat_trace = (int32_t *)dev[1];
+    a.d_trace = (int8_t *)dev[2];
+    a.s_trace = (int8_t *)dev[3];
     return LDPC_OK;
 }
 
@@ -1217,14 +1137,9 @@ static int rstat_run(ldpc_ctx *c, const ldpc::RstatArgs &a, bool f64)
     const ldpc::OptScope os(c->opts);
     const bool trace = a.err_trace || a.unsat_trace || a.d_trace || a.s_trace;
     const ldpc::RstatChoice ch = ldpc::rstat_choose(c->dg, f64, trace, c->g->maxdv, c->g->maxdc);
-    int slots = 0;
-    if (ch.slot_bytes) {
-        slots = (int)std::min<int64_t>((int64_t)a.batch * a.attempts, 2 * c->num_cus);
-        HIP_TRY(c->gscratch.ensure(ch.slot_bytes * (size_t)slots));
-    }
-    RC_TRY(c->begin_launch());
-    HIP_TRY(ldpc::rstat_launch(c->dg, a, f64, ch, c->gscratch.p, slots, c->num_cus, c->stream));
-    return c->end_launch();
+    return run_with_slots(*c, c->gscratch, ch, (int64_t)a.batch * a.attempts, 2 * c->num_cus, [&](void *scratch, int slots) {
+        return ldpc::rstat_launch(c->dg, a, f64, ch, scratch, slots, c->num_cus, c->stream);
+    });
 }
 
 int ldpc_rstat_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int batch, const ldpc_rstat_cfg *cfg,
@@ -1234,63 +1149,28 @@ int ldpc_rstat_decode_batch(ldpc_ctx *c, const void *y, const void *pert, int ba
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
     RC_TRY(rstat_check_cfg(cfg));
     RC_TRY(rstat_check_batch(c, cfg, batch));
-    if ((cfg->flags & LDPC_GDBF_NOISE) && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
+    const bool noise = cfg->flags & LDPC_GDBF_NOISE;
+    if (noise && !pert) return set_err(LDPC_ERR_INVALID, "NOISE needs pert");
     RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
-    const int N = c->g->N;
-    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
     ldpc::RstatArgs a;
-    RstatOuts o;
-    RC_TRY(rstat_fill(a, o, c, cfg, batch, attempts_out, trace, false));
-    a.src = ldpc::SRC_GIVEN;
-    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
-    if (cfg->flags & LDPC_GDBF_NOISE)
-        HIP_TRY(stage_in(pert, nb * (size_t)cfg->attempts * (size_t)cfg->T * fsz, c->p_stage, c->stream, a.pert));
-    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
-    OutStage d, w;
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    a.d_out = (int8_t *)d.dev;
-    a.frame_res = (int4 *)w.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    rstat_fill(a, c, cfg, batch);
+    SyncCall s(*c);
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));   // fetched first
+    RC_TRY(rstat_outs(s, c, a, attempts_out, trace));
+    RC_TRY(stage_given(s, c, a, f64, y, noise ? pert : nullptr,
+                       (size_t)batch * c->g->N * (size_t)cfg->attempts * (size_t)cfg->T, &a.pert, cw));
+    RC_TRY(s.snapshot());
     RC_TRY(rstat_run(c, a, f64));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    RC_TRY(rstat_fetch(c, o));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
-// y_out / pert_out / d_out: device pointers or null.
-static int rstat_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
-                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_out,
-                          const ldpc_rstat_trace *trace, bool device_only, RstatOuts &o, void *y_out, void *pert_out,
-                          int8_t *d_out, ldpc_frame_result *frames_dev)
+// After the checks and enter(); `a` holds the outputs.
+static int rstat_sim_run(ldpc_ctx *c, const SimCall &q, const ldpc_rstat_cfg *cfg, ldpc::RstatArgs &a)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(rstat_check_cfg(cfg));
-    RC_TRY(rstat_check_batch(c, cfg, batch));
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
-    // the attempt index takes the high word of the frame number in the Philox counter
-    if (first_cw > (1ull << 32) - (uint64_t)batch)
-        return set_err(LDPC_ERR_INVALID, "first_cw + batch must be <= 2^32");
-    RC_TRY(c->enter());
-    ldpc::RstatArgs a;
-    RC_TRY(rstat_fill(a, o, c, cfg, batch, attempts_out, trace, device_only));
-    a.src = ldpc::SRC_PHILOX;
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // newstat.cpp:192-193
-    a.sigma = std::sqrt(N0 / 2.0);
+    fill_sim(a, *c, q);                                       // newstat.cpp:192-193
+    fill_cw_table(a, *c);
     a.noise_sigma = a.sigma * cfg->noise_scale;               // :336
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
-    a.cw_rows = c->cw_rows;
-    a.y_out = y_out;
-    a.pert_out = pert_out;
-    a.d_out = d_out;
-    a.frame_res = (int4 *)frames_dev;
     return rstat_run(c, a, cfg->precision == LDPC_F64);
 }
 
@@ -1298,11 +1178,20 @@ int ldpc_rstat_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rsta
                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_attempt_result *attempts_dev,
                           const ldpc_rstat_trace *trace_dev, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev))
-        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
-    RstatOuts o;
-    return rstat_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, attempts_dev, trace_dev, true, o, nullptr,
-                          nullptr, nullptr, frames_dev);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(rstat_check_sim(c, cfg, q));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(require_device(attempts_dev, "attempts_out must be a device pointer"));
+    void *tp[4];
+    rstat_traces(trace_dev, tp);
+    for (void *p : tp) RC_TRY(require_device(p, "the traces must be device pointers"));
+    RC_TRY(c->enter());
+    ldpc::RstatArgs a;
+    rstat_fill(a, c, cfg, batch);
+    SyncCall s(*c);   // device pointers only: nothing is staged, nothing to fetch
+    RC_TRY(rstat_outs(s, c, a, attempts_dev, trace_dev));
+    a.frame_res = (int4 *)frames_dev;
+    return rstat_sim_run(c, q, cfg, a);
 }
 
 int ldpc_rstat_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
@@ -1310,29 +1199,22 @@ int ldpc_rstat_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat
                          ldpc_attempt_result *attempts_out, const ldpc_rstat_trace *trace, int8_t *d_out,
                          ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(rstat_check_cfg(cfg));
-    RC_TRY(rstat_check_batch(c, cfg, batch));
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(rstat_check_sim(c, cfg, q));
     RC_TRY(c->enter());
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    ldpc::RstatArgs a;
+    rstat_fill(a, c, cfg, batch);
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
     const size_t fsz = cfg->precision == LDPC_F64 ? 8 : 4, nb = (size_t)batch * c->g->N;
     const size_t pb = nb * (size_t)cfg->attempts * (size_t)cfg->T * fsz;
-    OutStage yo, po, d, w;
-    HIP_TRY(yo.bind(y_out, c->y_stage, nb * fsz));
-    HIP_TRY(po.bind(pert_out, c->p_stage, pb));
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    if (po.dev) HIP_TRY(hipMemsetAsync(po.dev, 0, pb, c->stream));   // rows that are not drawn
-    RstatOuts o;
-    RC_TRY(rstat_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, attempts_out, trace, false, o, yo.dev,
-                          po.dev, (int8_t *)d.dev, (ldpc_frame_result *)w.dev));
-    HIP_TRY(yo.fetch(c->stream));
-    HIP_TRY(po.fetch(c->stream));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    RC_TRY(rstat_fetch(c, o));
-    return c->counts_since(before, accum);
+    RC_TRY(s.out(y_out, c->y_stage, nb * fsz, a.y_out));
+    RC_TRY(s.out(pert_out, c->p_stage, pb, a.pert_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    if (a.pert_out) HIP_TRY(hipMemsetAsync(a.pert_out, 0, pb, c->stream));   // rows that are not drawn
+    RC_TRY(rstat_outs(s, c, a, attempts_out, trace));
+    RC_TRY(rstat_sim_run(c, q, cfg, a));
+    return s.finish(accum);
 }
 
 int ldpc_rstat_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_rstat_cfg *cfg, uint64_t seed,
@@ -1349,11 +1231,8 @@ int ldpc_rstat_kernel_info(ldpc_ctx *c, const ldpc_rstat_cfg *cfg, int with_trac
     RC_TRY(rstat_check_cfg(cfg));
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
-    const ldpc::RstatChoice ch =
-        ldpc::rstat_choose(c->dg, cfg->precision == LDPC_F64, with_trace != 0, c->g->maxdv, c->g->maxdc);
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
-    if (lds_bytes) *lds_bytes = ch.lds_bytes;
-    return LDPC_OK;
+    return report_choice(ldpc::rstat_choose(c->dg, cfg->precision == LDPC_F64, with_trace != 0, c->g->maxdv, c->g->maxdc),
+                         name, name_len, lds_bytes);
 }
 
 // ----------------------------------------------------------------- fixed-point NGDBF hardware model
@@ -1386,6 +1265,19 @@ static int hwgdbf_theta(double lmax, int nq)
     return (code >> (nq - 1)) & 1 ? -mag : mag;
 }
 
+// The kernel instance for cfg->qlen on the context's graph, or the refusal when one codeword's state exceeds LDS.
+static int hwgdbf_pick(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, ldpc::HwgdbfChoice &ch)
+{
+    const ldpc::OptScope os(c->opts);
+    ch = ldpc::hwgdbf_choose(c->dg, c->g->E, cfg->qlen);
+    if (!ch.name[0])
+        return set_err(LDPC_ERR_UNSUPPORTED,
+                       "NGDBFhw keeps a codeword in LDS: N + qlen + N + M = %d bytes exceed the bound of %d", ch.cw_bytes,
+                       ldpc::kHwgdbfMaxLds);
+    return LDPC_OK;
+}
+
+// Host work only (its refusals come before enter()).
 static int hwgdbf_fill(ldpc::HwgdbfArgs &a, ldpc::HwgdbfChoice &ch, ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, int batch)
 {
     std::memset((void *)&a, 0, sizeof a);
@@ -1403,16 +1295,8 @@ static int hwgdbf_fill(ldpc::HwgdbfArgs &a, ldpc::HwgdbfChoice &ch, ldpc_ctx *c,
     if (!(sm >= 0 && sm <= 65535)) return set_err(LDPC_ERR_INVALID, "Smult = round(NL / lmax) = %g out of range", sm);
     a.smult = (int)sm;
     a.theta = hwgdbf_theta(a.lmax, cfg->nq);
-    a.counts = (unsigned long long *)c->counts.p;
-    a.hist = (unsigned long long *)c->hist.p;
-    a.ticket = c->ticket();
-    const ldpc::OptScope os(c->opts);
-    ch = ldpc::hwgdbf_choose(c->dg, c->g->E, cfg->qlen);
-    if (!ch.name[0])
-        return set_err(LDPC_ERR_UNSUPPORTED,
-                       "NGDBFhw keeps a codeword in LDS: N + qlen + N + M = %d bytes exceed the bound of %d", ch.cw_bytes,
-                       ldpc::kHwgdbfMaxLds);
-    return LDPC_OK;
+    fill_accounting(a, *c);
+    return hwgdbf_pick(c, cfg, ch);
 }
 
 static int hwgdbf_run(ldpc_ctx *c, const ldpc::HwgdbfArgs &a, const ldpc::HwgdbfChoice &ch, bool f64)
@@ -1428,8 +1312,10 @@ int ldpc_hwgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *q, const in
 {
     if (!c || !y || !q) return set_err(LDPC_ERR_INVALID, "null argument");
     RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    RC_TRY(check_batch(*c, batch));
+    ldpc::HwgdbfArgs a;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_fill(a, ch, c, cfg, batch));
     const int N = c->g->N;
     if (qptr0 && !is_device_ptr(qptr0))   // a device array is clamped by the kernel
         for (int b = 0; b < batch; ++b)
@@ -1437,93 +1323,56 @@ int ldpc_hwgdbf_decode_batch(ldpc_ctx *c, const void *y, const void *q, const in
                 return set_err(LDPC_ERR_INVALID, "qptr0[%d] = %d outside [0, qlen - N = %d)", b, qptr0[b], cfg->qlen - N);
     RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
-    const size_t fsz = f64 ? 8 : 4, nb = (size_t)batch * N;
-    ldpc::HwgdbfArgs a;
-    ldpc::HwgdbfChoice ch;
-    RC_TRY(hwgdbf_fill(a, ch, c, cfg, batch));
-    a.src = ldpc::SRC_GIVEN;
-    HIP_TRY(stage_in(y, nb * fsz, c->y_stage, c->stream, a.y));
-    HIP_TRY(stage_in(q, (size_t)batch * cfg->qlen * fsz, c->p_stage, c->stream, a.q));
-    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
-    HIP_TRY(stage_in(qptr0, sizeof(int32_t) * (size_t)batch, c->hw_ptr_stage, c->stream, a.qptr0));
-    OutStage d, w, ir;
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    HIP_TRY(ir.bind(iters_run, c->hw_it_stage, sizeof(int32_t) * (size_t)batch));
-    a.d_out = (int8_t *)d.dev;
-    a.frame_res = (int4 *)w.dev;
-    a.iters_run = (int32_t *)ir.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, q, (size_t)batch * cfg->qlen, &a.q, cw));
+    RC_TRY(s.in(qptr0, sizeof(int32_t) * (size_t)batch, c->hw_ptr_stage, a.qptr0));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.out(iters_run, c->hw_it_stage, sizeof(int32_t) * (size_t)batch, a.iters_run));
+    RC_TRY(s.snapshot());
     RC_TRY(hwgdbf_run(c, a, ch, f64));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    HIP_TRY(ir.fetch(c->stream));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
-static int hwgdbf_sim_impl(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
-                           uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *q_out, int8_t *d_out,
-                           ldpc_frame_result *frames_dev)
+// The refusals of the ldpc_hwgdbf_sim_* calls that need no device, and the launch arguments of cfg.
+static int hwgdbf_sim_setup(ldpc_ctx *c, const SimCall &q, const ldpc_hwgdbf_cfg *cfg, ldpc::HwgdbfArgs &a,
+                            ldpc::HwgdbfChoice &ch)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    if (stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
-    RC_TRY(c->enter());
-    ldpc::HwgdbfArgs a;
-    ldpc::HwgdbfChoice ch;
-    RC_TRY(hwgdbf_fill(a, ch, c, cfg, batch));
-    a.src = ldpc::SRC_PHILOX;
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // NGDBFhw.cpp:127-129
-    a.sigma = std::sqrt(N0 / 2.0);
-    a.noise_sigma = a.sigma * cfg->noise_scale;
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.cw_table = c->cw_rows ? (const int8_t *)c->cw_table.p : nullptr;
-    a.cw_rows = c->cw_rows;
-    a.y_out = y_out;
-    a.q_out = q_out;
-    a.d_out = d_out;
-    a.frame_res = (int4 *)frames_dev;
-    return hwgdbf_run(c, a, ch, cfg->precision == LDPC_F64);
+    RC_TRY(check_sim(c, [&] { return hwgdbf_check_cfg(cfg, c->g->N); }, q, true));
+    RC_TRY(hwgdbf_fill(a, ch, c, cfg, q.batch));
+    const SimPoint pt = fill_sim(a, *c, q);                   // NGDBFhw.cpp:127-129
+    fill_cw_table(a, *c);
+    a.noise_sigma = pt.sigma * cfg->noise_scale;
+    return LDPC_OK;
 }
 
 int ldpc_hwgdbf_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
                            uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev))
-        return set_err(LDPC_ERR_INVALID, "frames_dev must be a device pointer");
-    return hwgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames_dev);
+    ldpc::HwgdbfArgs a;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    a.frame_res = (int4 *)frames_dev;
+    return hwgdbf_run(c, a, ch, cfg->precision == LDPC_F64);
 }
 
 int ldpc_hwgdbf_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
                           uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, void *q_out, int8_t *d_out,
                           ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    RC_TRY(hwgdbf_check_cfg(cfg, c->g->N));
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    ldpc::HwgdbfArgs a;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
     RC_TRY(c->enter());
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
-    const size_t fsz = cfg->precision == LDPC_F64 ? 8 : 4, nb = (size_t)batch * c->g->N;
-    OutStage yo, qo, d, w;
-    HIP_TRY(yo.bind(y_out, c->y_stage, nb * fsz));
-    HIP_TRY(qo.bind(q_out, c->p_stage, (size_t)batch * cfg->qlen * fsz));
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(w.bind(frames, c->fw_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    RC_TRY(hwgdbf_sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, yo.dev, qo.dev, (int8_t *)d.dev,
-                           (ldpc_frame_result *)w.dev));
-    HIP_TRY(yo.fetch(c->stream));
-    HIP_TRY(qo.fetch(c->stream));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(w.fetch(c->stream));
-    return c->counts_since(before, accum);
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    const size_t fsz = cfg->precision == LDPC_F64 ? 8 : 4;
+    RC_TRY(s.out(y_out, c->y_stage, (size_t)batch * c->g->N * fsz, a.y_out));
+    RC_TRY(s.out(q_out, c->p_stage, (size_t)batch * cfg->qlen * fsz, a.q_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(hwgdbf_run(c, a, ch, cfg->precision == LDPC_F64));
+    return s.finish(accum);
 }
 
 int ldpc_hwgdbf_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_hwgdbf_cfg *cfg, uint64_t seed,
@@ -1538,15 +1387,9 @@ int ldpc_hwgdbf_kernel_info(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, char *name,
 {
     RC_TRY(hwgdbf_check_cfg(cfg, c ? c->g->N : -1));
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    const ldpc::OptScope os(c->opts);
-    const ldpc::HwgdbfChoice ch = ldpc::hwgdbf_choose(c->dg, c->g->E, cfg->qlen);
-    if (!ch.name[0])
-        return set_err(LDPC_ERR_UNSUPPORTED,
-                       "NGDBFhw keeps a codeword in LDS: N + qlen + N + M = %d bytes exceed the bound of %d", ch.cw_bytes,
-                       ldpc::kHwgdbfMaxLds);
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
-    if (lds_bytes) *lds_bytes = ch.lds_bytes;
-    return LDPC_OK;
+    ldpc::HwgdbfChoice ch;
+    RC_TRY(hwgdbf_pick(c, cfg, ch));
+    return report_choice(ch, name, name_len, lds_bytes);
 }
 
 }  // extern "C"

@@ -1,15 +1,19 @@
 // host_rt.h -- the host runtime under both C ABIs (api.cpp: binary codes; nb_api.cpp:
-// GF(q)): error reporting, device buffers, host-or-device staging of inputs and
-// outputs, blob uploads, and CtxCore, the part of a context the two share (device,
-// streams, launch events, options, counters). Header only: both files include it.
+// GF(q)): error reporting, device buffers, blob uploads, CtxCore, the part of a context the two share (device, streams,
+// launch events, options, counters), and the call skeleton of the decoder entry points
+// (the checks every family makes, the simulated point, SyncCall, run_with_slots). Header
+// only: both files include it.
 #pragma once
 #include "ldpc_hip.h"
 #include "blob.h"
 #include "check.h"
+#include "kernels.h"
 #include "options.h"
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
@@ -89,39 +93,6 @@ inline bool is_device_ptr(const void *p)
         return false;
     }
     return at.type == hipMemoryTypeDevice || at.type == hipMemoryTypeManaged;
-}
-
-// An output the caller may hold on the host or on the device: the kernel writes dev (the
-// caller's own pointer, or the staging buffer when that is host memory; null: not wanted),
-// and fetch() copies a staged output back once the launch is queued.
-struct OutStage {
-    void *user = nullptr, *dev = nullptr;
-    size_t bytes = 0;
-    hipError_t bind(void *out, DevBuf &stage, size_t n)
-    {
-        user = dev = out;
-        bytes = n;
-        if (!out || is_device_ptr(out)) return hipSuccess;
-        const hipError_t e = stage.ensure(n);
-        dev = stage.p;
-        return e;
-    }
-    hipError_t fetch(hipStream_t s) const
-    {
-        return dev == user ? hipSuccess : hipMemcpyAsync(user, dev, bytes, hipMemcpyDeviceToHost, s);
-    }
-};
-
-// Its input counterpart: dev is where the kernel reads the n bytes of `in` -- `in` itself
-// when that is device memory (or null), else the staging buffer, with the copy queued on s.
-template <class T> hipError_t stage_in(const T *in, size_t n, DevBuf &stage, hipStream_t s, const T *&dev)
-{
-    dev = in;
-    if (!in || is_device_ptr(in)) return hipSuccess;
-    const hipError_t e = stage.ensure(n);
-    if (e != hipSuccess) return e;
-    dev = (const T *)stage.p;
-    return hipMemcpyAsync(stage.p, in, n, hipMemcpyHostToDevice, s);
 }
 
 // The device copy of a blob: one allocation, one copy; sections are at buf.p + their offsets.
@@ -278,5 +249,148 @@ struct CtxCore {
         return LDPC_OK;
     }
 };
+
+// ---- The call skeleton of the decoder entry points. Every family refuses in one order:
+// null context or required pointer, cfg, batch, the simulated point (R, stream_id,
+// first_cw), device-pointer requirements; then enter() and the first device call.
+inline int check_batch(const CtxCore &c, int batch)
+{
+    if (batch <= 0 || batch > c.max_batch)
+        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c.max_batch);
+    return LDPC_OK;
+}
+// The arguments every fused Monte-Carlo entry point takes: frames first_cw .. first_cw + batch - 1
+// of the Philox stream (seed, stream_id) at Eb/N0 for rate R.
+struct SimCall {
+    double ebn0_db, R;
+    uint64_t seed;
+    uint32_t stream_id;
+    uint64_t first_cw;
+    int batch;
+};
+// stream20: the GDBF families keep 20 bits of stream_id beside the iteration in a Philox word.
+inline int check_sim_point(const SimCall &q, bool stream20)
+{
+    if (!(q.R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
+    if (stream20 && q.stream_id >= (1u << 20)) return set_err(LDPC_ERR_INVALID, "stream_id must be < 2^20");
+    return LDPC_OK;
+}
+// The refusals of a *_sim_* call that need no device, in order; check_cfg() is the family's own.
+template <class Ctx, class CheckCfg> int check_sim(const Ctx *c, CheckCfg check_cfg, const SimCall &q, bool stream20)
+{
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    RC_TRY(check_cfg());
+    RC_TRY(check_batch(*c, q.batch));
+    return check_sim_point(q, stream20);
+}
+// What an asynchronous launch writes must be device memory (null: not wanted).
+inline int require_device(const void *p, const char *refusal)
+{
+    return p && !is_device_ptr(p) ? set_err(LDPC_ERR_INVALID, "%s", refusal) : LDPC_OK;
+}
+
+// N0 and sigma of Eb/N0 at rate R, in double as every reference program has them
+// (decodeMinSum.cpp:146-147, decodeGDBF.cpp:175-176, RNGDBF.cpp:167-168, newstat.cpp:192-193,
+// NGDBFhw.cpp:127-129).
+struct SimPoint {
+    double N0, sigma;
+};
+inline SimPoint sim_point(double ebn0_db, double R)
+{
+    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;
+    return {N0, std::sqrt(N0 / 2.0)};
+}
+
+// The *Args of the kernel families spell their common fields alike. The accounting of the
+// binary GDBF families: counters, error-weight histogram, codeword ticket.
+template <class Args, class Ctx> void fill_accounting(Args &a, Ctx &c)
+{
+    a.counts = (unsigned long long *)c.counts.p;
+    a.hist = (unsigned long long *)c.hist.p;
+    a.ticket = c.ticket();
+}
+// The fused Monte-Carlo source of a launch; returns the point for the family's own noise terms.
+template <class Args, class Ctx> SimPoint fill_sim(Args &a, Ctx &c, const SimCall &q)
+{
+    const SimPoint pt = sim_point(q.ebn0_db, q.R);
+    a.src = SRC_PHILOX;
+    a.sigma = (decltype(a.sigma))pt.sigma;
+    a.seed = q.seed;
+    a.stream_id = q.stream_id;
+    a.first_cw = q.first_cw;
+    return pt;
+}
+// ... and the codeword table it sends (the binary contexts; null: the all-zero codeword).
+template <class Args, class Ctx> void fill_cw_table(Args &a, Ctx &c)
+{
+    a.cw_table = c.cw_rows ? (const int8_t *)c.cw_table.p : nullptr;
+    a.cw_rows = c.cw_rows;
+}
+
+// A synchronous entry point: snapshot() reads the counters before the launch; out() gives
+// the device address of an output the caller holds on the host or on the device (its own
+// pointer, or the staging buffer when that is host memory; null: not wanted) and in() that
+// of a given-sample input; finish() copies the staged outputs back in the order they were
+// bound and adds what the launch counted to acc (null: not wanted; waits for the stream).
+struct SyncCall {
+    CtxCore &c;
+    unsigned long long before[kCountWords];
+    struct {
+        void *user, *dev;
+        size_t bytes;
+    } staged[12];
+    int n = 0;
+    explicit SyncCall(CtxCore &ctx) : c(ctx) {}
+    int snapshot() { return c.read_counts_raw(before); }
+    // forced: the kernel needs the buffer although the caller does not want it
+    template <class D> int out(void *user, DevBuf &stage, size_t bytes, D *&dev, bool forced = false)
+    {
+        dev = (D *)user;
+        if (user ? is_device_ptr(user) : !forced) return LDPC_OK;
+        HIP_TRY(stage.ensure(bytes));
+        dev = (D *)stage.p;
+        if (user) staged[n++] = {user, stage.p, bytes};
+        return LDPC_OK;
+    }
+    template <class T> int in(const T *user, size_t bytes, DevBuf &stage, const T *&dev)
+    {
+        dev = user;
+        if (!user || is_device_ptr(user)) return LDPC_OK;
+        HIP_TRY(stage.ensure(bytes));
+        dev = (const T *)stage.p;
+        HIP_TRY(hipMemcpyAsync(stage.p, user, bytes, hipMemcpyHostToDevice, c.stream));
+        return LDPC_OK;
+    }
+    template <class Counts> int finish(Counts *acc)
+    {
+        for (int i = 0; i < n; ++i)
+            HIP_TRY(hipMemcpyAsync(staged[i].user, staged[i].dev, staged[i].bytes, hipMemcpyDeviceToHost, c.stream));
+        return c.counts_since(before, acc);
+    }
+};
+
+// A launch between the context's launch events, with the scratch of a kernel that keeps
+// its state in global memory: choice.slot_bytes for each of min(items, max_slots) resident
+// items (no bytes: no slots). launch(scratch, slots) queues the family's kernels.
+template <class Choice, class Launch>
+int run_with_slots(CtxCore &c, DevBuf &scratch, const Choice &ch, int64_t items, int max_slots, Launch launch)
+{
+    int slots = 0;
+    if (ch.slot_bytes) {
+        slots = (int)std::min<int64_t>(items, max_slots);
+        HIP_TRY(scratch.ensure(ch.slot_bytes * (size_t)slots));
+    }
+    RC_TRY(c.begin_launch());
+    HIP_TRY(launch(scratch.p, slots));
+    return c.end_launch();
+}
+
+// The tail of the *_kernel_info calls.
+template <class Choice> int report_choice(const Choice &ch, char *name, int name_len, int *lds_bytes)
+{
+    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
+    if (lds_bytes) *lds_bytes = ch.lds_bytes;
+    return LDPC_OK;
+}
 
 }  // namespace ldpc

@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-using namespace ldpc;   // host_rt.h: set_err, HIP_TRY, DevBuf, OutStage, stage_in, CtxCore, Blob
+using namespace ldpc;   // host_rt.h: set_err, HIP_TRY, DevBuf, CtxCore, Blob and the call skeleton
 
 struct ldpc_nb_ctx : CtxCore {
     const ldpc_nb_graph *g = nullptr;
@@ -159,8 +159,7 @@ void ldpc_nb_ctx_destroy(ldpc_nb_ctx *c)
 static int check_ems(const ldpc_nb_ctx *c, const ldpc_ems_cfg *cfg, int batch)
 {
     if (!c || !cfg) return set_err(LDPC_ERR_INVALID, "null argument");
-    if (batch <= 0 || batch > c->max_batch)
-        return set_err(LDPC_ERR_INVALID, "batch %d outside 1..max_batch=%d", batch, c->max_batch);
+    RC_TRY(check_batch(*c, batch));
     if (cfg->T < 0) return set_err(LDPC_ERR_INVALID, "T must be >= 0");
     if (cfg->nm < 1) return set_err(LDPC_ERR_INVALID, "nm must be >= 1");
     if (!(cfg->offset >= 0)) return set_err(LDPC_ERR_INVALID, "offset must be >= 0");
@@ -171,18 +170,13 @@ static int run(ldpc_nb_ctx *c, const ldpc::NbArgs &a)
 {
     const ldpc::OptScope os(c->opts);
     const ldpc::NbChoice ch = ldpc::nb_choose(c->dg, c->g->maxdc);
-    int slots = 0;
-    if (ch.slot_bytes) {
-        slots = std::min(a.batch, c->num_cus);
-        HIP_TRY(c->scratch.ensure(ch.slot_bytes * (size_t)slots));
-    }
-    RC_TRY(c->begin_launch());
     ldpc::NbDevGraph dg = c->dg;
     // untruncated messages (nm >= q): the XOR-swizzled layout; truncation ranks
     // entries by symbol on ties, so it keeps the plain one (nb.hip vn_lane)
     if (a.nm >= dg.q && nb_swizzle_enabled()) dg.col_h = c->col_h_swz;
-    HIP_TRY(ldpc::nb_launch(dg, a, ch, c->scratch.p, slots, c->num_cus, c->stream));
-    return c->end_launch();
+    return run_with_slots(*c, c->scratch, ch, a.batch, c->num_cus, [&](void *scratch, int slots) {
+        return ldpc::nb_launch(dg, a, ch, scratch, slots, c->num_cus, c->stream);
+    });
 }
 
 static void fill_cfg(ldpc::NbArgs &a, ldpc_nb_ctx *c, const ldpc_ems_cfg *cfg, int batch)
@@ -195,6 +189,13 @@ static void fill_cfg(ldpc::NbArgs &a, ldpc_nb_ctx *c, const ldpc_ems_cfg *cfg, i
     a.offset = (float)cfg->offset;
     a.counts = (unsigned long long *)c->counts.p;
     a.ticket = c->ticket();
+}
+
+// The decided symbols and the frame records, host or device.
+static int bind_decisions(SyncCall &s, ldpc_nb_ctx *c, ldpc::NbArgs &a, uint8_t *d_out, ldpc_frame_result *frames)
+{
+    RC_TRY(s.out(d_out, c->d_stage, (size_t)a.batch * c->g->N, a.d_out));
+    return s.out(frames, c->fr_stage, sizeof(ldpc_frame_result) * (size_t)a.batch, a.frame_res);
 }
 
 int ldpc_ems_decode_batch(ldpc_nb_ctx *c, const float *y, int batch, double n0, const ldpc_ems_cfg *cfg,
@@ -210,73 +211,61 @@ int ldpc_ems_decode_batch(ldpc_nb_ctx *c, const float *y, int batch, double n0, 
     a.src = ldpc::SRC_GIVEN;
     a.n0 = (float)n0;
     const size_t nb = (size_t)batch * N;
-    HIP_TRY(stage_in(y, nb * m * sizeof(float), c->y_stage, c->stream, a.y));
-    HIP_TRY(stage_in(cw, nb, c->c_stage, c->stream, a.c));
+    SyncCall s(*c);
+    RC_TRY(s.in(y, nb * m * sizeof(float), c->y_stage, a.y));
+    RC_TRY(s.in(cw, nb, c->c_stage, a.c));
     if (a.c != cw)   // staged, so cw is host memory: its symbols can be checked (before anything reads the copy)
         for (size_t i = 0; i < nb; ++i)
             if (cw[i] >= (unsigned)c->g->q)
                 return set_err(LDPC_ERR_INVALID, "codeword symbol %zu is %d (q=%d)", i, cw[i], c->g->q);
-    OutStage d, f;
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(f.bind(frames, c->fr_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    a.d_out = (uint8_t *)d.dev;
-    a.frame_res = (int4 *)f.dev;
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
     RC_TRY(run(c, a));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(f.fetch(c->stream));
-    return c->counts_since(before, counts);
+    return s.finish(counts);
 }
 
-static int sim_impl(ldpc_nb_ctx *c, double ebn0_db, double R, const ldpc_ems_cfg *cfg, uint64_t seed,
-                    uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev, float *y_dev,
-                    uint8_t *d_dev)
+// The refusals of the ldpc_ems_sim_* calls that need no device (check_ems keeps its own order).
+static int check_ems_sim(const ldpc_nb_ctx *c, const ldpc_ems_cfg *cfg, const SimCall &q)
 {
-    RC_TRY(check_ems(c, cfg, batch));
-    if (!(R > 0)) return set_err(LDPC_ERR_INVALID, "rate must be > 0");
-    RC_TRY(c->enter());
-    ldpc::NbArgs a;
-    fill_cfg(a, c, cfg, batch);
-    a.src = ldpc::SRC_PHILOX;
-    const double N0 = std::pow(10.0, -ebn0_db / 10.0) / R;   // decodeMinSum.cpp:146-147
-    a.n0 = (float)N0;
-    a.sigma = (float)std::sqrt(N0 / 2.0);
-    a.seed = seed;
-    a.stream_id = stream_id;
-    a.first_cw = first_cw;
-    a.frame_res = (int4 *)frames_dev;
-    a.y_out = y_dev;
-    a.d_out = d_dev;
+    RC_TRY(check_ems(c, cfg, q.batch));
+    return check_sim_point(q, false);
+}
+
+// After the checks and enter(); `a` holds the outputs.
+static int sim_run(ldpc_nb_ctx *c, const SimCall &q, ldpc::NbArgs &a)
+{
+    a.n0 = (float)fill_sim(a, *c, q).N0;   // decodeMinSum.cpp:146-147
     return run(c, a);
 }
 
 int ldpc_ems_sim_launch(ldpc_nb_ctx *c, double ebn0_db, double R, const ldpc_ems_cfg *cfg, uint64_t seed,
                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    if (frames_dev && !is_device_ptr(frames_dev)) return set_err(LDPC_ERR_INVALID, "frames_dev must be device memory");
-    return sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev, nullptr, nullptr);
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_ems_sim(c, cfg, q));
+    RC_TRY(require_device(frames_dev, "frames_dev must be device memory"));
+    RC_TRY(c->enter());
+    ldpc::NbArgs a;
+    fill_cfg(a, c, cfg, batch);
+    a.frame_res = (int4 *)frames_dev;
+    return sim_run(c, q, a);
 }
 
 int ldpc_ems_sim_trace(ldpc_nb_ctx *c, double ebn0_db, double R, const ldpc_ems_cfg *cfg, uint64_t seed,
                        uint32_t stream_id, uint64_t first_cw, int batch, float *y_out, uint8_t *d_out,
                        ldpc_frame_result *frames, ldpc_nb_counts *accum)
 {
-    RC_TRY(check_ems(c, cfg, batch));
+    const SimCall q{ebn0_db, R, seed, stream_id, first_cw, batch};
+    RC_TRY(check_ems_sim(c, cfg, q));
     RC_TRY(c->enter());
-    const size_t nb = (size_t)batch * c->g->N;
-    OutStage y, d, f;
-    HIP_TRY(y.bind(y_out, c->y_stage, nb * c->g->m * sizeof(float)));
-    HIP_TRY(d.bind(d_out, c->d_stage, nb));
-    HIP_TRY(f.bind(frames, c->fr_stage, sizeof(ldpc_frame_result) * (size_t)batch));
-    unsigned long long before[kCountWords];
-    RC_TRY(c->read_counts_raw(before));
-    RC_TRY(sim_impl(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, (ldpc_frame_result *)f.dev, (float *)y.dev,
-                    (uint8_t *)d.dev));
-    HIP_TRY(y.fetch(c->stream));
-    HIP_TRY(d.fetch(c->stream));
-    HIP_TRY(f.fetch(c->stream));
-    return c->counts_since(before, accum);
+    ldpc::NbArgs a;
+    fill_cfg(a, c, cfg, batch);
+    SyncCall s(*c);
+    RC_TRY(s.out(y_out, c->y_stage, (size_t)batch * c->g->N * c->g->m * sizeof(float), a.y_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
+    RC_TRY(sim_run(c, q, a));
+    return s.finish(accum);
 }
 
 int ldpc_ems_sim_batch(ldpc_nb_ctx *c, double ebn0_db, double R, const ldpc_ems_cfg *cfg, uint64_t seed,
@@ -302,10 +291,7 @@ int ldpc_ems_kernel_info(ldpc_nb_ctx *c, char *name, int name_len, int *lds_byte
 {
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     const ldpc::OptScope os(c->opts);
-    const ldpc::NbChoice ch = ldpc::nb_choose(c->dg, c->g->maxdc);
-    if (name && name_len > 0) std::snprintf(name, (size_t)name_len, "%s", ch.name);
-    if (lds_bytes) *lds_bytes = ch.lds_bytes;
-    return LDPC_OK;
+    return report_choice(ldpc::nb_choose(c->dg, c->g->maxdc), name, name_len, lds_bytes);
 }
 
 int ldpc_nb_ctx_set_option(ldpc_nb_ctx *c, int option, int value)

@@ -281,6 +281,88 @@ class EmsConfig:
         return _EmsCfg(self.T, self.nm, int(self.early_stop), 0, self.offset)
 
 
+_vp, _i32, _u32, _u64, _dbl = C.c_void_p, C.c_int, C.c_uint32, C.c_uint64, C.c_double
+_pi32 = C.POINTER(C.c_int)
+
+
+def _sim(cfg, *outs):
+    """Argument types of a *_sim_* call: ctx, Eb/N0, R, cfg, seed, stream_id, first_cw, batch, then its outputs."""
+    return [_vp, _dbl, _dbl, C.POINTER(cfg), _u64, _u32, _u64, _i32, *outs]
+
+
+def _info(cfg, *more):
+    return [_vp, C.POINTER(cfg), *more, C.c_char_p, _i32, _pi32]
+
+
+# Every symbol include/ldpc_hip.h declares (tests/test_abi.py compares the two): (argument types, result type).
+_SIG = {
+    "ldpc_abi_version": ([], _i32),
+    "ldpc_f64_nms_fast_division": ([_dbl], _i32),
+    "ldpc_bp_math_probe": ([_i32, _vp, _i32, _vp, _vp], _i32),
+    "ldpc_check_selftest": ([_i32], _i32),
+    "ldpc_last_error": ([], C.c_char_p),
+    "ldpc_graph_create": ([_i32, _i32, _vp, _vp, _vp, _vp, C.POINTER(_vp)], _i32),
+    "ldpc_graph_load_alist": ([C.c_char_p, C.POINTER(_vp)], _i32),
+    "ldpc_graph_info": ([_vp] + [_pi32] * 5, _i32),
+    "ldpc_graph_destroy": ([_vp], None),
+    "ldpc_graph_layers": ([_vp, _vp, _vp, _pi32], _i32),
+    "ldpc_device_count": ([_pi32], _i32),
+    "ldpc_ctx_create": ([_i32, _vp, _i32, C.POINTER(_vp)], _i32),
+    "ldpc_ctx_set_stream": ([_vp, _vp], _i32),
+    "ldpc_ctx_synchronize": ([_vp], _i32),
+    "ldpc_ctx_destroy": ([_vp], None),
+    "ldpc_decode_batch": ([_vp, _vp, _i32, C.POINTER(_Cfg), _vp, _vp, _vp, C.POINTER(Counts)], _i32),
+    "ldpc_sim_set_codewords": ([_vp, _vp, _i32], _i32),
+    "ldpc_sim_launch": (_sim(_Cfg, _vp), _i32),
+    "ldpc_ctx_read_counts": ([_vp, C.POINTER(Counts), _i32], _i32),
+    "ldpc_ctx_read_histogram": ([_vp, _vp, _i32], _i32),
+    "ldpc_sim_batch": (_sim(_Cfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_sim_trace": (_sim(_Cfg, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_ctx_last_kernel_ms": ([_vp, C.POINTER(C.c_float)], _i32),
+    "ldpc_ctx_kernel_info": (_info(_Cfg) + [_pi32], _i32),
+    "ldpc_ctx_redo_count": ([_vp, C.POINTER(C.c_int64)], _i32),
+    "ldpc_ctx_row_sched_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
+    "ldpc_ctx_set_option": ([_vp, _i32, _i32], _i32),
+    "ldpc_ctx_get_option": ([_vp, _i32, _pi32], _i32),
+    "ldpc_nb_ctx_set_option": ([_vp, _i32, _i32], _i32),
+    "ldpc_gdbf_decode_batch": ([_vp, _vp, _vp, _i32, C.POINTER(_GdbfCfg), _vp, _vp, _vp, C.POINTER(Counts)], _i32),
+    "ldpc_gdbf_sim_launch": (_sim(_GdbfCfg, _vp), _i32),
+    "ldpc_gdbf_sim_batch": (_sim(_GdbfCfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_gdbf_kernel_info": (_info(_GdbfCfg), _i32),
+    "ldpc_rgdbf_decode_batch": ([_vp, _vp, _vp, _i32, C.POINTER(_RgdbfCfg), _vp, _vp, _vp, C.POINTER(Counts)], _i32),
+    "ldpc_rgdbf_sim_launch": (_sim(_RgdbfCfg, _vp), _i32),
+    "ldpc_rgdbf_sim_batch": (_sim(_RgdbfCfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_rgdbf_kernel_info": (_info(_RgdbfCfg), _i32),
+    "ldpc_rstat_decode_batch": ([_vp, _vp, _vp, _i32, C.POINTER(_RstatCfg), _vp, _vp, C.POINTER(_RstatTrace), _vp,
+                                 _vp, C.POINTER(Counts)], _i32),
+    "ldpc_rstat_sim_launch": (_sim(_RstatCfg, _vp, C.POINTER(_RstatTrace), _vp), _i32),
+    "ldpc_rstat_sim_batch": (_sim(_RstatCfg, _vp, C.POINTER(_RstatTrace), _vp, C.POINTER(Counts)), _i32),
+    "ldpc_rstat_sim_trace": (_sim(_RstatCfg, _vp, _vp, _vp, C.POINTER(_RstatTrace), _vp, _vp, C.POINTER(Counts)),
+                              _i32),
+    "ldpc_rstat_kernel_info": (_info(_RstatCfg, _i32), _i32),
+    "ldpc_hwgdbf_decode_batch": ([_vp, _vp, _vp, _vp, _i32, C.POINTER(_HwGdbfCfg), _vp, _vp, _vp, _vp,
+                                  C.POINTER(Counts)], _i32),
+    "ldpc_hwgdbf_sim_launch": (_sim(_HwGdbfCfg, _vp), _i32),
+    "ldpc_hwgdbf_sim_batch": (_sim(_HwGdbfCfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_hwgdbf_sim_trace": (_sim(_HwGdbfCfg, _vp, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_hwgdbf_kernel_info": (_info(_HwGdbfCfg), _i32),
+    "ldpc_nb_graph_create": ([_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)], _i32),
+    "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(_vp)], _i32),
+    "ldpc_nb_graph_info": ([_vp] + [_pi32] * 6, _i32),
+    "ldpc_nb_graph_destroy": ([_vp], None),
+    "ldpc_nb_ctx_create": ([_i32, _vp, _i32, C.POINTER(_vp)], _i32),
+    "ldpc_nb_ctx_set_stream": ([_vp, _vp], _i32),
+    "ldpc_nb_ctx_destroy": ([_vp], None),
+    "ldpc_nb_ctx_read_counts": ([_vp, C.POINTER(NbCounts), _i32], _i32),
+    "ldpc_nb_ctx_last_kernel_ms": ([_vp, C.POINTER(C.c_float)], _i32),
+    "ldpc_ems_kernel_info": ([_vp, C.c_char_p, _i32, _pi32], _i32),
+    "ldpc_ems_decode_batch": ([_vp, _vp, _i32, _dbl, C.POINTER(_EmsCfg), _vp, _vp, _vp, C.POINTER(NbCounts)], _i32),
+    "ldpc_ems_sim_launch": (_sim(_EmsCfg, _vp), _i32),
+    "ldpc_ems_sim_batch": (_sim(_EmsCfg, _vp, C.POINTER(NbCounts)), _i32),
+    "ldpc_ems_sim_trace": (_sim(_EmsCfg, _vp, _vp, _vp, C.POINTER(NbCounts)), _i32),
+}
+EXPORTED = list(_SIG)
+
 _lib = None
 
 
@@ -299,84 +381,7 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    vp, i32, i64, u32, u64, dbl = C.c_void_p, C.c_int, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
-    sig = {
-        "ldpc_abi_version": ([], i32),
-        "ldpc_f64_nms_fast_division": ([dbl], i32),
-        "ldpc_bp_math_probe": ([i32, vp, i32, vp, vp], i32),
-        "ldpc_check_selftest": ([i32], i32),
-        "ldpc_last_error": ([], C.c_char_p),
-        "ldpc_graph_create": ([i32, i32, vp, vp, vp, vp, C.POINTER(vp)], i32),
-        "ldpc_graph_load_alist": ([C.c_char_p, C.POINTER(vp)], i32),
-        "ldpc_graph_info": ([vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
-                             C.POINTER(i32)], i32),
-        "ldpc_graph_destroy": ([vp], None),
-        "ldpc_graph_layers": ([vp, vp, vp, C.POINTER(i32)], i32),
-        "ldpc_device_count": ([C.POINTER(i32)], i32),
-        "ldpc_ctx_create": ([i32, vp, i32, C.POINTER(vp)], i32),
-        "ldpc_ctx_set_stream": ([vp, vp], i32),
-        "ldpc_ctx_synchronize": ([vp], i32),
-        "ldpc_ctx_destroy": ([vp], None),
-        "ldpc_decode_batch": ([vp, vp, i32, C.POINTER(_Cfg), vp, vp, vp, C.POINTER(Counts)], i32),
-        "ldpc_sim_set_codewords": ([vp, vp, i32], i32),
-        "ldpc_sim_launch": ([vp, dbl, dbl, C.POINTER(_Cfg), u64, u32, u64, i32, vp], i32),
-        "ldpc_ctx_read_counts": ([vp, C.POINTER(Counts), i32], i32),
-        "ldpc_ctx_read_histogram": ([vp, vp, i32], i32),
-        "ldpc_sim_batch": ([vp, dbl, dbl, C.POINTER(_Cfg), u64, u32, u64, i32, vp, C.POINTER(Counts)], i32),
-        "ldpc_sim_trace": ([vp, dbl, dbl, C.POINTER(_Cfg), u64, u32, u64, i32, vp, vp, vp, C.POINTER(Counts)],
-                           i32),
-        "ldpc_ctx_last_kernel_ms": ([vp, C.POINTER(C.c_float)], i32),
-        "ldpc_ctx_kernel_info": ([vp, C.POINTER(_Cfg), C.c_char_p, i32, C.POINTER(i32), C.POINTER(i32)], i32),
-        "ldpc_ctx_redo_count": ([vp, C.POINTER(C.c_int64)], i32),
-        "ldpc_ctx_row_sched_info": ([vp, C.POINTER(_Cfg), vp], i32),
-        "ldpc_ctx_set_option": ([vp, i32, i32], i32),
-        "ldpc_ctx_get_option": ([vp, i32, C.POINTER(i32)], i32),
-        "ldpc_nb_ctx_set_option": ([vp, i32, i32], i32),
-        "ldpc_gdbf_decode_batch": ([vp, vp, vp, i32, C.POINTER(_GdbfCfg), vp, vp, vp, C.POINTER(Counts)], i32),
-        "ldpc_gdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_GdbfCfg), u64, u32, u64, i32, vp], i32),
-        "ldpc_gdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_GdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
-                                i32),
-        "ldpc_gdbf_kernel_info": ([vp, C.POINTER(_GdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
-        "ldpc_rgdbf_decode_batch": ([vp, vp, vp, i32, C.POINTER(_RgdbfCfg), vp, vp, vp, C.POINTER(Counts)], i32),
-        "ldpc_rgdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp], i32),
-        "ldpc_rgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_RgdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
-                                 i32),
-        "ldpc_rgdbf_kernel_info": ([vp, C.POINTER(_RgdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
-        "ldpc_rstat_decode_batch": ([vp, vp, vp, i32, C.POINTER(_RstatCfg), vp, vp, C.POINTER(_RstatTrace), vp, vp,
-                                     C.POINTER(Counts)], i32),
-        "ldpc_rstat_sim_launch": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, C.POINTER(_RstatTrace),
-                                   vp], i32),
-        "ldpc_rstat_sim_batch": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, C.POINTER(_RstatTrace),
-                                  vp, C.POINTER(Counts)], i32),
-        "ldpc_rstat_sim_trace": ([vp, dbl, dbl, C.POINTER(_RstatCfg), u64, u32, u64, i32, vp, vp, vp,
-                                  C.POINTER(_RstatTrace), vp, vp, C.POINTER(Counts)], i32),
-        "ldpc_rstat_kernel_info": ([vp, C.POINTER(_RstatCfg), i32, C.c_char_p, i32, C.POINTER(i32)], i32),
-        "ldpc_hwgdbf_decode_batch": ([vp, vp, vp, vp, i32, C.POINTER(_HwGdbfCfg), vp, vp, vp, vp, C.POINTER(Counts)],
-                                     i32),
-        "ldpc_hwgdbf_sim_launch": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp], i32),
-        "ldpc_hwgdbf_sim_batch": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp, C.POINTER(Counts)],
-                                  i32),
-        "ldpc_hwgdbf_sim_trace": ([vp, dbl, dbl, C.POINTER(_HwGdbfCfg), u64, u32, u64, i32, vp, vp, vp, vp,
-                                   C.POINTER(Counts)], i32),
-        "ldpc_hwgdbf_kernel_info": ([vp, C.POINTER(_HwGdbfCfg), C.c_char_p, i32, C.POINTER(i32)], i32),
-        "ldpc_nb_graph_create": ([i32, i32, i32, vp, vp, vp, vp, vp, vp, C.POINTER(vp)], i32),
-        "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(vp)], i32),
-        "ldpc_nb_graph_info": ([vp] + [C.POINTER(i32)] * 6, i32),
-        "ldpc_nb_graph_destroy": ([vp], None),
-        "ldpc_nb_ctx_create": ([i32, vp, i32, C.POINTER(vp)], i32),
-        "ldpc_nb_ctx_set_stream": ([vp, vp], i32),
-        "ldpc_nb_ctx_destroy": ([vp], None),
-        "ldpc_nb_ctx_read_counts": ([vp, C.POINTER(NbCounts), i32], i32),
-        "ldpc_nb_ctx_last_kernel_ms": ([vp, C.POINTER(C.c_float)], i32),
-        "ldpc_ems_kernel_info": ([vp, C.c_char_p, i32, C.POINTER(i32)], i32),
-        "ldpc_ems_decode_batch": ([vp, vp, i32, dbl, C.POINTER(_EmsCfg), vp, vp, vp, C.POINTER(NbCounts)], i32),
-        "ldpc_ems_sim_launch": ([vp, dbl, dbl, C.POINTER(_EmsCfg), u64, u32, u64, i32, vp], i32),
-        "ldpc_ems_sim_batch": ([vp, dbl, dbl, C.POINTER(_EmsCfg), u64, u32, u64, i32, vp, C.POINTER(NbCounts)],
-                               i32),
-        "ldpc_ems_sim_trace": ([vp, dbl, dbl, C.POINTER(_EmsCfg), u64, u32, u64, i32, vp, vp, vp,
-                                C.POINTER(NbCounts)], i32),
-    }
-    for name, (argt, rest) in sig.items():
+    for name, (argt, rest) in _SIG.items():
         fn = getattr(L, name)
         fn.argtypes = argt
         fn.restype = rest
@@ -384,25 +389,6 @@ def lib():
         raise ImportError(f"{LIB_PATH}: ABI version {L.ldpc_abi_version()}, this binding needs {ABI_VERSION}")
     _lib = L
     return L
-
-
-# Every symbol include/ldpc_hip.h declares (checked by tests/test_abi.py).
-EXPORTED = ["ldpc_abi_version", "ldpc_f64_nms_fast_division", "ldpc_bp_math_probe", "ldpc_check_selftest", "ldpc_last_error", "ldpc_graph_create", "ldpc_graph_load_alist",
-            "ldpc_graph_info", "ldpc_graph_destroy", "ldpc_graph_layers", "ldpc_device_count", "ldpc_ctx_create",
-            "ldpc_ctx_set_stream", "ldpc_ctx_synchronize", "ldpc_ctx_destroy", "ldpc_decode_batch",
-            "ldpc_sim_set_codewords", "ldpc_sim_launch", "ldpc_ctx_read_counts", "ldpc_ctx_read_histogram",
-            "ldpc_sim_batch", "ldpc_sim_trace", "ldpc_ctx_last_kernel_ms", "ldpc_ctx_kernel_info", "ldpc_ctx_redo_count",
-            "ldpc_ctx_row_sched_info", "ldpc_ctx_set_option", "ldpc_ctx_get_option", "ldpc_nb_ctx_set_option",
-            "ldpc_gdbf_decode_batch", "ldpc_gdbf_sim_launch", "ldpc_gdbf_sim_batch", "ldpc_gdbf_kernel_info",
-            "ldpc_rgdbf_decode_batch", "ldpc_rgdbf_sim_launch", "ldpc_rgdbf_sim_batch", "ldpc_rgdbf_kernel_info",
-            "ldpc_rstat_decode_batch", "ldpc_rstat_sim_launch", "ldpc_rstat_sim_batch", "ldpc_rstat_sim_trace",
-            "ldpc_rstat_kernel_info",
-            "ldpc_hwgdbf_decode_batch", "ldpc_hwgdbf_sim_launch", "ldpc_hwgdbf_sim_batch", "ldpc_hwgdbf_sim_trace",
-            "ldpc_hwgdbf_kernel_info",
-            "ldpc_nb_graph_create", "ldpc_nb_graph_load_alist", "ldpc_nb_graph_info", "ldpc_nb_graph_destroy",
-            "ldpc_nb_ctx_create", "ldpc_nb_ctx_set_stream", "ldpc_nb_ctx_destroy", "ldpc_nb_ctx_read_counts",
-            "ldpc_nb_ctx_last_kernel_ms", "ldpc_ems_kernel_info", "ldpc_ems_decode_batch", "ldpc_ems_sim_launch",
-            "ldpc_ems_sim_batch", "ldpc_ems_sim_trace"]
 
 
 def _check(rc: int):
@@ -472,6 +458,39 @@ def _ptr(a) -> Optional[int]:
             raise ValueError("tensor must be contiguous")
         return a.data_ptr()
     raise TypeError(type(a))
+
+
+def _given(N: int, cfg, y, c=None):
+    """The float inputs of a *_decode call as the library reads them: y as a contiguous
+    [batch, N] array of the cfg's precision and the optional bipolar codewords c as
+    contiguous int8. Returns (y, batch, c, dtype); further inputs take the same dtype."""
+    want = np.float64 if cfg.precision == F64 else np.float32
+    y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
+    if c is not None:
+        c = np.ascontiguousarray(c, dtype=np.int8)
+    return y, y.shape[0], c, want
+
+
+def _sim_launch(fn, h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, *outs_dev):
+    """An asynchronous *_sim_launch: every output is a device tensor or None."""
+    _check(fn(h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch, *(_ptr(o) for o in outs_dev)))
+
+
+def _sim_batch(fn, h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, *outs, want_frames=True, counts=None):
+    """A synchronous *_sim_batch / *_sim_trace: `outs` (host arrays or ctypes arguments, in the
+    call's order), then the frame records (None unless wanted) and the counts. Returns (frames, counts)."""
+    fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
+    cnt = (counts or Counts)()
+    outs = [_ptr(o) if isinstance(o, np.ndarray) else o for o in outs]
+    _check(fn(h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch, *outs, _ptr(fr), C.byref(cnt)))
+    return fr, cnt
+
+
+def _kernel_info(fn, *args) -> dict:
+    name = C.create_string_buffer(32)
+    lds = C.c_int()
+    _check(fn(*args, name, 32, C.byref(lds)))
+    return {"kernel": name.value.decode(), "lds_bytes": lds.value}
 
 
 class Context:
@@ -560,16 +579,12 @@ class Context:
 
     def sim_launch(self, ebn0_db: float, R: float, cfg: DecoderConfig, seed: int, stream_id: int, first_cw: int,
                    batch: int, frames_dev=None):
-        _check(lib().ldpc_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                     _ptr(frames_dev)))
+        _sim_launch(lib().ldpc_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
 
     def sim_batch(self, ebn0_db: float, R: float, cfg: DecoderConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int, want_frames: bool = True):
-        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
-        cnt = Counts()
-        _check(lib().ldpc_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                    _ptr(fr), C.byref(cnt)))
-        return fr, cnt
+        return _sim_batch(lib().ldpc_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
 
     def sim_trace(self, ebn0_db: float, R: float, cfg: DecoderConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int):
@@ -577,10 +592,7 @@ class Context:
         N = self.graph.N
         y = np.empty((batch, N), dtype=np.float64 if cfg.precision == F64 else np.float32)
         d = np.empty((batch, N), dtype=np.int8)
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
-        _check(lib().ldpc_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                    y.ctypes.data, d.ctypes.data, fr.ctypes.data, C.byref(cnt)))
+        fr, cnt = _sim_batch(lib().ldpc_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, y, d)
         return y, d, fr, cnt
 
     def read_counts(self, reset: bool = False) -> Counts:
@@ -619,81 +631,57 @@ class Context:
         return {"kernel": name.value.decode(), "lds_bytes": lds.value, "blocks_per_cu": bpc.value}
 
     # ---- GDBF / NGDBF (src/decodeGDBF.cpp) ----
+    def _decode(self, fn, y, cfg, c, want_decisions, *ins):
+        """A *_decode_batch call with d, frames and counts as its outputs; `ins` follow y."""
+        batch = y.shape[0]
+        d = np.empty((batch, self.graph.N), dtype=np.int8) if want_decisions else None
+        fr = np.empty(batch, dtype=FRAME_DTYPE)
+        cnt = Counts()
+        _check(fn(self._h, _ptr(y), *(_ptr(a) for a in ins), batch, C.byref(cfg._c()), _ptr(c), _ptr(d), _ptr(fr),
+                  C.byref(cnt)))
+        return d, fr, cnt
+
     def gdbf_decode(self, y, pert, cfg: GdbfConfig, c=None, want_decisions: bool = True):
         """Decode raw channel samples y[batch, N] with perturbations pert[batch, T, N] (or None
         without GDBF_NOISE). Returns (d, frames (iters = iterations run), Counts)."""
-        N = self.graph.N
-        want = np.float64 if cfg.precision == F64 else np.float32
-        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
-        batch = y.shape[0]
+        y, batch, c, want = _given(self.graph.N, cfg, y, c)
         if pert is not None:
-            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.T, N)
-        if c is not None:
-            c = np.ascontiguousarray(c, dtype=np.int8)
-        d = np.empty((batch, N), dtype=np.int8) if want_decisions else None
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
-        _check(lib().ldpc_gdbf_decode_batch(self._h, _ptr(y), _ptr(pert), batch, C.byref(cfg._c()), _ptr(c),
-                                            _ptr(d), _ptr(fr), C.byref(cnt)))
-        return d, fr, cnt
+            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.T, self.graph.N)
+        return self._decode(lib().ldpc_gdbf_decode_batch, y, cfg, c, want_decisions, pert)
 
     def gdbf_sim_launch(self, ebn0_db: float, R: float, cfg: GdbfConfig, seed: int, stream_id: int, first_cw: int,
                         batch: int, frames_dev=None):
-        _check(lib().ldpc_gdbf_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                          _ptr(frames_dev)))
+        _sim_launch(lib().ldpc_gdbf_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
 
     def gdbf_sim_batch(self, ebn0_db: float, R: float, cfg: GdbfConfig, seed: int, stream_id: int, first_cw: int,
                        batch: int, want_frames: bool = True):
-        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
-        cnt = Counts()
-        _check(lib().ldpc_gdbf_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                         _ptr(fr), C.byref(cnt)))
-        return fr, cnt
+        return _sim_batch(lib().ldpc_gdbf_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
 
     def gdbf_kernel_info(self, cfg: GdbfConfig) -> dict:
-        name = C.create_string_buffer(32)
-        lds = C.c_int()
-        _check(lib().ldpc_gdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
-        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+        return _kernel_info(lib().ldpc_gdbf_kernel_info, self._h, C.byref(cfg._c()))
 
     # ---- re-decoding NGDBF (src/RNGDBF.cpp) ----
     def rgdbf_decode(self, y, pert, cfg: RgdbfConfig, c=None, want_decisions: bool = True):
         """Decode raw channel samples y[batch, N] with perturbations pert[batch, maxphase*T, N]
         (row phase*T + it; None without GDBF_NOISE). Returns (d, frames, Counts); iters are
         sums over the phases (rgdbf_phases gives the phase count)."""
-        N = self.graph.N
-        want = np.float64 if cfg.precision == F64 else np.float32
-        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
-        batch = y.shape[0]
+        y, batch, c, want = _given(self.graph.N, cfg, y, c)
         if pert is not None:
-            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.maxphase * cfg.T, N)
-        if c is not None:
-            c = np.ascontiguousarray(c, dtype=np.int8)
-        d = np.empty((batch, N), dtype=np.int8) if want_decisions else None
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
-        _check(lib().ldpc_rgdbf_decode_batch(self._h, _ptr(y), _ptr(pert), batch, C.byref(cfg._c()), _ptr(c),
-                                             _ptr(d), _ptr(fr), C.byref(cnt)))
-        return d, fr, cnt
+            pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.maxphase * cfg.T, self.graph.N)
+        return self._decode(lib().ldpc_rgdbf_decode_batch, y, cfg, c, want_decisions, pert)
 
     def rgdbf_sim_launch(self, ebn0_db: float, R: float, cfg: RgdbfConfig, seed: int, stream_id: int, first_cw: int,
                          batch: int, frames_dev=None):
-        _check(lib().ldpc_rgdbf_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                           _ptr(frames_dev)))
+        _sim_launch(lib().ldpc_rgdbf_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
 
     def rgdbf_sim_batch(self, ebn0_db: float, R: float, cfg: RgdbfConfig, seed: int, stream_id: int, first_cw: int,
                         batch: int, want_frames: bool = True):
-        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
-        cnt = Counts()
-        _check(lib().ldpc_rgdbf_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                          _ptr(fr), C.byref(cnt)))
-        return fr, cnt
+        return _sim_batch(lib().ldpc_rgdbf_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
 
     def rgdbf_kernel_info(self, cfg: RgdbfConfig) -> dict:
-        name = C.create_string_buffer(32)
-        lds = C.c_int()
-        _check(lib().ldpc_rgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
-        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+        return _kernel_info(lib().ldpc_rgdbf_kernel_info, self._h, C.byref(cfg._c()))
 
     # ---- every attempt of every frame (src/newstat.cpp, src/replayGDBF.cpp) ----
     def _rstat_trace(self, batch: int, cfg: RstatConfig, want: bool):
@@ -713,13 +701,9 @@ class Context:
         syndrome_fail are the last attempt's and iters the sum over the attempts; trace is a
         dict of err_trace, unsat_trace, d_trace, s_trace (None unless want_trace)."""
         N = self.graph.N
-        want = np.float64 if cfg.precision == F64 else np.float32
-        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
-        batch = y.shape[0]
+        y, batch, c, want = _given(N, cfg, y, c)
         if pert is not None:
             pert = np.ascontiguousarray(pert, dtype=want).reshape(batch, cfg.attempts, cfg.T, N)
-        if c is not None:
-            c = np.ascontiguousarray(c, dtype=np.int8)
         att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
         d = np.empty((batch, N), dtype=np.int8)
         fr = np.empty(batch, dtype=FRAME_DTYPE)
@@ -738,19 +722,17 @@ class Context:
             unknown = set(trace_dev) - {k for k, _ in _RstatTrace._fields_}
             if unknown:
                 raise KeyError(f"unknown trace {sorted(unknown)}")
-            targ = C.byref(_RstatTrace(*(_ptr(trace_dev.get(k)) for k, _ in _RstatTrace._fields_)))
+            targ = _RstatTrace(*(_ptr(trace_dev.get(k)) for k, _ in _RstatTrace._fields_))
         _check(lib().ldpc_rstat_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                           _ptr(attempts_dev), targ, _ptr(frames_dev)))
+                                           _ptr(attempts_dev), targ and C.byref(targ), _ptr(frames_dev)))
 
     def rstat_sim(self, ebn0_db: float, R: float, cfg: RstatConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int, want_trace: bool = False):
         """Fused Monte-Carlo of batch frames x cfg.attempts attempts: (attempts, frames, Counts, trace)."""
         att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
         targ, tr = self._rstat_trace(batch, cfg, want_trace)
-        _check(lib().ldpc_rstat_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                          _ptr(att), targ, _ptr(fr), C.byref(cnt)))
+        fr, cnt = _sim_batch(lib().ldpc_rstat_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                             att, targ)
         return att, fr, cnt, tr
 
     def rstat_sim_trace(self, ebn0_db: float, R: float, cfg: RstatConfig, seed: int, stream_id: int, first_cw: int,
@@ -763,18 +745,13 @@ class Context:
         pert = np.empty((batch, cfg.attempts, cfg.T, N), dtype=want)
         att = np.empty((batch, cfg.attempts), dtype=ATTEMPT_DTYPE)
         d = np.empty((batch, N), dtype=np.int8)
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
         targ, tr = self._rstat_trace(batch, cfg, want_trace)
-        _check(lib().ldpc_rstat_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                          _ptr(y), _ptr(pert), _ptr(att), targ, _ptr(d), _ptr(fr), C.byref(cnt)))
+        fr, cnt = _sim_batch(lib().ldpc_rstat_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                             y, pert, att, targ, d)
         return y, pert, att, d, fr, cnt, tr
 
     def rstat_kernel_info(self, cfg: RstatConfig, with_trace: bool = False) -> dict:
-        name = C.create_string_buffer(32)
-        lds = C.c_int()
-        _check(lib().ldpc_rstat_kernel_info(self._h, C.byref(cfg._c()), int(with_trace), name, 32, C.byref(lds)))
-        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+        return _kernel_info(lib().ldpc_rstat_kernel_info, self._h, C.byref(cfg._c()), int(with_trace))
 
     # ---- fixed-point NGDBF hardware model (src/NGDBFhw.cpp) ----
     def hwgdbf_decode(self, y, q, cfg: HwGdbfConfig, qptr0=None, c=None, want_decisions: bool = True):
@@ -783,14 +760,10 @@ class Context:
         iters_run, Counts): frames[].bit_err / iters are the least over the phases, iters_run
         the sum of the phases' iterations (what a caller adds to the pointer)."""
         N = self.graph.N
-        want = np.float64 if cfg.precision == F64 else np.float32
-        y = np.ascontiguousarray(y, dtype=want).reshape(-1, N)
-        batch = y.shape[0]
+        y, batch, c, want = _given(N, cfg, y, c)
         q = np.ascontiguousarray(q, dtype=want).reshape(batch, cfg.qlen)
         if qptr0 is not None:
             qptr0 = np.ascontiguousarray(qptr0, dtype=np.int32).reshape(batch)
-        if c is not None:
-            c = np.ascontiguousarray(c, dtype=np.int8)
         d = np.empty((batch, N), dtype=np.int8) if want_decisions else None
         fr = np.empty(batch, dtype=FRAME_DTYPE)
         run = np.empty(batch, dtype=np.int32)
@@ -801,16 +774,12 @@ class Context:
 
     def hwgdbf_sim_launch(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int,
                           first_cw: int, batch: int, frames_dev=None):
-        _check(lib().ldpc_hwgdbf_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                            _ptr(frames_dev)))
+        _sim_launch(lib().ldpc_hwgdbf_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
 
     def hwgdbf_sim_batch(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int, first_cw: int,
                          batch: int, want_frames: bool = True):
-        fr = np.empty(batch, dtype=FRAME_DTYPE) if want_frames else None
-        cnt = Counts()
-        _check(lib().ldpc_hwgdbf_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                           _ptr(fr), C.byref(cnt)))
-        return fr, cnt
+        return _sim_batch(lib().ldpc_hwgdbf_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
 
     def hwgdbf_sim_trace(self, ebn0_db: float, R: float, cfg: HwGdbfConfig, seed: int, stream_id: int, first_cw: int,
                          batch: int):
@@ -820,18 +789,12 @@ class Context:
         y = np.empty((batch, N), dtype=want)
         q = np.empty((batch, cfg.qlen), dtype=want)
         d = np.empty((batch, N), dtype=np.int8)
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = Counts()
-        _check(lib().ldpc_hwgdbf_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                           y.ctypes.data, q.ctypes.data, d.ctypes.data, fr.ctypes.data,
-                                           C.byref(cnt)))
+        fr, cnt = _sim_batch(lib().ldpc_hwgdbf_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                             y, q, d)
         return y, q, d, fr, cnt
 
     def hwgdbf_kernel_info(self, cfg: HwGdbfConfig) -> dict:
-        name = C.create_string_buffer(32)
-        lds = C.c_int()
-        _check(lib().ldpc_hwgdbf_kernel_info(self._h, C.byref(cfg._c()), name, 32, C.byref(lds)))
-        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+        return _kernel_info(lib().ldpc_hwgdbf_kernel_info, self._h, C.byref(cfg._c()))
 
 
 # ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ----
@@ -919,26 +882,20 @@ class NbContext:
 
     def sim_launch(self, ebn0_db: float, R: float, cfg: EmsConfig, seed: int, stream_id: int, first_cw: int,
                    batch: int, frames_dev=None):
-        _check(lib().ldpc_ems_sim_launch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                         _ptr(frames_dev)))
+        _sim_launch(lib().ldpc_ems_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
 
     def sim_batch(self, ebn0_db: float, R: float, cfg: EmsConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int):
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = NbCounts()
-        _check(lib().ldpc_ems_sim_batch(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                        fr.ctypes.data, C.byref(cnt)))
-        return fr, cnt
+        return _sim_batch(lib().ldpc_ems_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          counts=NbCounts)
 
     def sim_trace(self, ebn0_db: float, R: float, cfg: EmsConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int):
         g = self.graph
         y = np.empty((batch, g.N * g.m), dtype=np.float32)
         d = np.empty((batch, g.N), dtype=np.uint8)
-        fr = np.empty(batch, dtype=FRAME_DTYPE)
-        cnt = NbCounts()
-        _check(lib().ldpc_ems_sim_trace(self._h, ebn0_db, R, C.byref(cfg._c()), seed, stream_id, first_cw, batch,
-                                        y.ctypes.data, d.ctypes.data, fr.ctypes.data, C.byref(cnt)))
+        fr, cnt = _sim_batch(lib().ldpc_ems_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, y, d,
+                             counts=NbCounts)
         return y, d, fr, cnt
 
     def read_counts(self, reset: bool = False) -> NbCounts:
@@ -952,7 +909,4 @@ class NbContext:
         return float(ms.value)
 
     def kernel_info(self) -> dict:
-        name = C.create_string_buffer(32)
-        lds = C.c_int()
-        _check(lib().ldpc_ems_kernel_info(self._h, name, 32, C.byref(lds)))
-        return {"kernel": name.value.decode(), "lds_bytes": lds.value}
+        return _kernel_info(lib().ldpc_ems_kernel_info, self._h)

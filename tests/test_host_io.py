@@ -6,7 +6,9 @@ included) and a mix must give bit-identical decisions, frame records and counts.
 
 Shapes are the smallest that reach the real kernels; the Eb/N0 values (0.8 dB min-sum,
 2.0 dB GDBF, 1.0 dB EMS, all used by other tests on these codes) leave failing frames,
-so the outputs compared are not trivial."""
+so the outputs compared are not trivial. The re-decoding, every-attempt and hardware-model
+calls run PEG at batch 5 with T 20, two phases / three attempts, in fp64, at their own
+tests' Eb/N0 on this code (3.0 dB; NGDBFhw 5.8 dB at its hard-coded rate)."""
 import ctypes as C
 import math
 
@@ -80,8 +82,8 @@ def _three_ways(call, sync, inputs, outputs, cnt_type, mixed_host=()):
     return res[0]
 
 
-def _channel(shape, ebn0, dtype, seed):
-    sigma = math.sqrt(10 ** (-ebn0 / 10) / 0.5 / 2)
+def _channel(shape, ebn0, dtype, seed, R=0.5):
+    sigma = math.sqrt(10 ** (-ebn0 / 10) / R / 2)
     rng = np.random.default_rng(seed)
     return (1 + sigma * rng.standard_normal(shape)).astype(dtype), sigma
 
@@ -207,3 +209,130 @@ def test_ems_sim_trace_host_and_device_outputs(nbctx):
 
     (y, d, fr), cnt = _host_and_device(call, nbctx.read_counts, outs, native.NbCounts)
     assert cnt[3] == B and fr["bit_err"].sum() > 0 and int((d != 0).sum()) == cnt[6] and y.std() > 0.5
+
+
+# ---- the families whose staging no test exercised with device-side arguments
+RB, RT, PHASES, ATTEMPTS = 5, 20, 2, 3
+HW_R, HW_SNR = 0.8413, 5.8          # NGDBFhw.cpp's hard-coded rate; tests/test_hwgdbf.py's Eb/N0 on PEG
+
+
+@pytest.mark.gpu
+def test_rgdbf_decode_batch_host_device_mixed(gpu_ctx_factory):
+    native = _native()
+    L = native.lib()
+    ctx = gpu_ctx_factory(PEG)
+    N = ctx.graph.N
+    cfg = native.RgdbfConfig(T=RT, maxphase=PHASES)._c()
+    y, sigma = _channel((RB, N), 3.0, np.float64, seed=5)
+    pert = 0.75 * sigma * np.random.default_rng(6).standard_normal((RB, PHASES * RT, N))
+    cw = np.ones((RB, N), dtype=np.int8)
+    outs = [np.zeros((RB, N), dtype=np.int8), np.zeros(RB, dtype=native.FRAME_DTYPE)]
+
+    def call(py, ppert, pcw, pd, pfr, pcnt):
+        return L.ldpc_rgdbf_decode_batch(ctx._h, py, ppert, RB, C.byref(cfg), pcw, pd, pfr, pcnt)
+
+    (d, fr), cnt = _three_ways(call, ctx.synchronize, dict(y=y, pert=pert, cw=cw), outs, native.Counts,
+                               mixed_host=("pert", "cw"))
+    assert cnt[3] == RB and fr["bit_err"].sum() > 0 and int((d != 1).sum()) == fr["bit_err"].sum() == cnt[0]
+    assert fr["iters"].max() > RT                                       # a second phase ran
+
+
+def _rstat_outputs(native, N, M, samples):
+    shape = (RB, ATTEMPTS, RT)
+    outs = [np.zeros((RB, ATTEMPTS), dtype=native.ATTEMPT_DTYPE), np.zeros(shape, dtype=np.int32),
+            np.zeros(shape, dtype=np.int32), np.zeros(shape + (N,), dtype=np.int8), np.zeros(shape + (M,), dtype=np.int8),
+            np.zeros((RB, N), dtype=np.int8), np.zeros(RB, dtype=native.FRAME_DTYPE)]
+    if samples:
+        outs = [np.zeros((RB, N)), np.zeros((RB, ATTEMPTS, RT, N))] + outs
+    return outs
+
+
+def _rstat_asserts(att, err, unsat, dtr, strc, d, fr, cnt):
+    assert cnt[3] == RB and fr["bit_err"].sum() > 0 and int((d != 1).sum()) == fr["bit_err"].sum()
+    assert (att["iters"].sum(axis=1) == fr["iters"]).all() and (att["bit_err"][:, -1] == fr["bit_err"]).all()
+    ran = err >= 0                                                      # -1: the row's iteration did not run
+    assert ran.any() and (ran == (unsat >= 0)).all()
+    assert (np.abs(dtr).max(axis=3) == ran).all() and (np.abs(strc).max(axis=3) == ran).all()   # +-1 rows / zero rows
+
+
+@pytest.mark.gpu
+def test_rstat_decode_batch_host_device_mixed(gpu_ctx_factory):
+    native = _native()
+    L = native.lib()
+    ctx = gpu_ctx_factory(PEG)
+    N, M = ctx.graph.N, ctx.graph.M
+    cfg = native.RstatConfig(T=RT, attempts=ATTEMPTS)._c()
+    y, sigma = _channel((RB, N), 3.0, np.float64, seed=7)
+    pert = 0.75 * sigma * np.random.default_rng(8).standard_normal((RB, ATTEMPTS, RT, N))
+    cw = np.ones((RB, N), dtype=np.int8)
+
+    def call(py, ppert, pcw, patt, perr, punsat, pdt, pst, pd, pfr, pcnt):
+        tr = native._RstatTrace(perr, punsat, pdt, pst)
+        return L.ldpc_rstat_decode_batch(ctx._h, py, ppert, RB, C.byref(cfg), pcw, patt, C.byref(tr), pd, pfr, pcnt)
+
+    outs, cnt = _three_ways(call, ctx.synchronize, dict(y=y, pert=pert, cw=cw), _rstat_outputs(native, N, M, False),
+                            native.Counts, mixed_host=("pert", "cw"))
+    _rstat_asserts(*outs, cnt)
+
+
+@pytest.mark.gpu
+def test_rstat_sim_trace_host_and_device_outputs(gpu_ctx_factory):
+    native = _native()
+    L = native.lib()
+    ctx = gpu_ctx_factory(PEG)
+    N, M = ctx.graph.N, ctx.graph.M
+    cfg = native.RstatConfig(T=RT, attempts=ATTEMPTS)._c()
+
+    def call(py, ppert, patt, perr, punsat, pdt, pst, pd, pfr, pcnt):
+        tr = native._RstatTrace(perr, punsat, pdt, pst)
+        return L.ldpc_rstat_sim_trace(ctx._h, 3.0, 0.5, C.byref(cfg), 9, 1, 3, RB, py, ppert, patt, C.byref(tr), pd, pfr,
+                                      pcnt)
+
+    (y, pert, *outs), cnt = _host_and_device(call, ctx.synchronize, _rstat_outputs(native, N, M, True), native.Counts)
+    _rstat_asserts(*outs, cnt)
+    assert y.std() > 0.5 and pert[:, 0, 0].std() > 0.1                  # the samples drawn came back
+
+
+def _hw_cfg(native, N):
+    return native.HwGdbfConfig(T=RT, maxphase=PHASES, qlen=N + 7)       # tests/test_hwgdbf.py "wraps": T 20, qlen N + 7
+
+
+@pytest.mark.gpu
+def test_hwgdbf_decode_batch_host_device_mixed(gpu_ctx_factory):
+    native = _native()
+    L = native.lib()
+    ctx = gpu_ctx_factory(PEG)
+    N = ctx.graph.N
+    hw = _hw_cfg(native, N)
+    cfg = hw._c()
+    y, sigma = _channel((RB, N), HW_SNR, np.float64, seed=10, R=HW_R)
+    q = hw.noise_scale * sigma * np.random.default_rng(11).standard_normal((RB, hw.qlen))
+    qptr0 = np.array([0, 6, 3, 1, 5], dtype=np.int32)                   # each in [0, qlen - N)
+    cw = np.ones((RB, N), dtype=np.int8)
+    outs = [np.zeros((RB, N), dtype=np.int8), np.zeros(RB, dtype=native.FRAME_DTYPE), np.zeros(RB, dtype=np.int32)]
+
+    def call(py, pq, pqptr, pcw, pd, pfr, prun, pcnt):
+        return L.ldpc_hwgdbf_decode_batch(ctx._h, py, pq, pqptr, RB, C.byref(cfg), pcw, pd, pfr, prun, pcnt)
+
+    (d, fr, run), cnt = _three_ways(call, ctx.synchronize, dict(y=y, q=q, qptr0=qptr0, cw=cw), outs, native.Counts,
+                                    mixed_host=("q", "qptr0"))
+    assert cnt[3] == RB and fr["bit_err"].sum() > 0 and (d != 1).any()
+    assert (run >= fr["iters"]).all() and run.max() > RT                # the sum over the phases; a second phase ran
+
+
+@pytest.mark.gpu
+def test_hwgdbf_sim_trace_host_and_device_outputs(gpu_ctx_factory):
+    native = _native()
+    L = native.lib()
+    ctx = gpu_ctx_factory(PEG)
+    N = ctx.graph.N
+    hw = _hw_cfg(native, N)
+    cfg = hw._c()
+    outs = [np.zeros((RB, N)), np.zeros((RB, hw.qlen)), np.zeros((RB, N), dtype=np.int8),
+            np.zeros(RB, dtype=native.FRAME_DTYPE)]
+
+    def call(py, pq, pd, pfr, pcnt):
+        return L.ldpc_hwgdbf_sim_trace(ctx._h, HW_SNR, HW_R, C.byref(cfg), 12, 1, 3, RB, py, pq, pd, pfr, pcnt)
+
+    (y, q, d, fr), cnt = _host_and_device(call, ctx.synchronize, outs, native.Counts)
+    assert cnt[3] == RB and fr["bit_err"].sum() > 0 and (d != 1).any() and y.std() > 0.1 and q.std() > 0.1
