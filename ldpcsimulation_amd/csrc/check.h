@@ -38,8 +38,8 @@ enum CheckSite : unsigned {
     CHK_BP_MSG,            // bp_rows: message slot                         (< E + 1)
     CHK_DDBMP_EDGE,        // ddbmp: flag byte of an edge in its row's slot  (< rows * stride)
     CHK_DDBMP_CHECK,       // ddbmp: parity byte of a check                 (< rows)
-    CHK_RGDBF_BIT,         // rgdbf_rows: flag byte a check row gathers     (< np)
-    CHK_RGDBF_PARITY,      // rgdbf_rows: parity byte a bit reads / a row writes (< M + 1)
+    CHK_RGDBF_BIT,         // rgdbf: decision byte a check gathers (rgdbf_lds / _global < N, rgdbf_rows < np)
+    CHK_RGDBF_PARITY,      // rgdbf: parity byte a bit reads / a row writes (rgdbf_lds / _global < M, rgdbf_rows < M + 1)
     CHK_HWGDBF_BIT,        // hwgdbf: decision byte a check gathers             (< N)
     CHK_HWGDBF_CHECK,      // hwgdbf: parity byte a bit reads                   (< M)
     CHK_HWGDBF_NOISE,      // hwgdbf: noise sample i + qpointer a bit reads     (< qlen)

@@ -30,11 +30,15 @@ struct GdbfArgs {
                                     // this counter (gdbf_launch zeroes it): early stop makes them unequal
 };
 
+// The kernel a launch takes; one struct for gdbf.hip, rgdbf.hip (RgdbfChoice) and rstat.hip
+// (RstatChoice): a register-schedule kernel ("gdbf_rows", "rgdbf_rows", "rstat_rows"), or one
+// workgroup per item with its state in LDS ("gdbf_lds", "rgdbf_lds", "rstat_wg") or in a
+// global slot ("gdbf_global", "rgdbf_global", "rstat_wg").
 struct GdbfChoice {
-    const char *name = "";          // "gdbf_rows" | "gdbf_lds" | "gdbf_global"
+    const char *name = "";
     int lds_bytes = 0, threads = 0;
-    size_t slot_bytes = 0;          // global kernel: state bytes per resident codeword
-    int dvm = 0;                    // gdbf_rows: bit-degree bound of the register schedule (4 or 12)
+    size_t slot_bytes = 0;          // global-slot kernel: state bytes per resident item
+    int dvm = 0;                    // register schedule: its bit-degree bound (4 or 12), else 0
 };
 
 // flags: the decoder's GDBF_* switches; maxdv / maxdc: the code's largest

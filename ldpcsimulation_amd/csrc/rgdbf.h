@@ -13,12 +13,7 @@ struct RgdbfArgs : GdbfArgs {
 
 constexpr int kRgdbfFlags = GDBF_NOISE | GDBF_ADAPT | GDBF_WEIGHT | GDBF_SMOOTH | GDBF_SATURATE;
 
-struct RgdbfChoice {
-    const char *name = "";          // "rgdbf_rows" | "rgdbf_lds" | "rgdbf_global"
-    int lds_bytes = 0, threads = 0;
-    size_t slot_bytes = 0;          // global kernel: state bytes per resident codeword
-    int dvm = 0;                    // rgdbf_rows: bit-degree bound of the register schedule (4 or 12)
-};
+using RgdbfChoice = GdbfChoice;     // "rgdbf_rows" | "rgdbf_lds" | "rgdbf_global"
 
 // maxdv / maxdc: the code's largest column / row degree. Option LDPC_OPT_GDBF_KERNEL = 1
 // forces the one-workgroup-per-codeword kernels here as it does for gdbf.hip.

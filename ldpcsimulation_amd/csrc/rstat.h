@@ -25,12 +25,7 @@ struct RstatArgs : GdbfArgs {
     int8_t *d_trace, *s_trace;      // [..][N] / [..][M], +-1
 };
 
-struct RstatChoice {
-    const char *name = "";          // "rstat_rows" | "rstat_wg"
-    int lds_bytes = 0, threads = 0;
-    size_t slot_bytes = 0;          // rstat_wg with its state in a global slot: bytes per resident item
-    int dvm = 0;                    // rstat_rows: bit-degree bound of the register schedule (4 or 12)
-};
+using RstatChoice = GdbfChoice;     // "rstat_rows" | "rstat_wg" (in LDS, or in a global slot: slot_bytes > 0)
 
 // rstat_rows on the codes rgdbf_rows takes when no trace is wanted (maxdv / maxdc: the code's
 // largest column / row degree); option LDPC_OPT_GDBF_KERNEL = 1 forces rstat_wg.

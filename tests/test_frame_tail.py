@@ -135,3 +135,61 @@ def test_gdbf(runs, N, prec):
     ctx.reset_options()
     assert np.array_equal(frames["gdbf_rows"], frames["gdbf_lds"])
     assert np.array_equal(frames["gdbf_rows"]["uncoded_bit_err"], r["ms_lds"]["fr"]["uncoded_bit_err"])
+
+
+# The re-decoding family on these codes. What the N % 4 == 0 fixtures never reach in its
+# register-schedule kernels: a cut last Philox group, M = 63 < 512 (most lanes own no row and all
+# of row slot 1 is padding), NT = 512 with DVM = 4, and the stop flag's parity across a restart
+# with odd T. theta = -0.6, alpha = 0.96 (the golden runs' PEG settings), lambda 0.99, noise scale
+# 0.75, Ymax 2.5; window 3 so that smoothing starts inside the T = 5 iterations. At 0 dB hardly a
+# frame of these codes decodes in 5 iterations, so frames restart and attempts differ by their
+# noise alone; both are asserted.
+NGDBF = dict(T=T, theta=-0.6, lambda_=0.99, alpha=0.96, noise_scale=0.75, ymax=2.5, windowsize=3)
+MAXPHASE, ATTEMPTS = 3, 3
+
+
+@pytest.mark.parametrize("N,prec", CASES)
+def test_rgdbf(runs, N, prec):
+    """rgdbf_rows against rgdbf_lds: frame records and counters equal, with frames that run
+    more than one phase; the uncoded column is the min-sum trace's."""
+    r = runs(N, prec)
+    ctx = r["ctx"]
+    cfg = native.RgdbfConfig(maxphase=MAXPHASE, precision=PREC[prec][0], **NGDBF)
+    frames, counts = {}, {}
+    for opt, kernel in ((0, "rgdbf_rows"), (1, "rgdbf_lds")):
+        ctx.reset_options()
+        ctx.set_option("gdbf_kernel", opt)
+        assert ctx.rgdbf_kernel_info(cfg)["kernel"] == kernel
+        frames[kernel], cnt = ctx.rgdbf_sim_batch(EBN0, RATE, cfg, SEED, STREAM, FIRST_CW, BATCH)
+        counts[kernel] = cnt.as_array()
+        assert cnt.frames == BATCH and cnt.uncoded_bit_err == int(frames[kernel]["uncoded_bit_err"].sum())
+    ctx.reset_options()
+    assert (native.rgdbf_phases(frames["rgdbf_lds"]["iters"], T, MAXPHASE) > 1).any()
+    assert np.array_equal(frames["rgdbf_rows"], frames["rgdbf_lds"])
+    assert np.array_equal(counts["rgdbf_rows"], counts["rgdbf_lds"])
+    assert np.array_equal(frames["rgdbf_rows"]["uncoded_bit_err"], r["ms_lds"]["fr"]["uncoded_bit_err"])
+
+
+@pytest.mark.parametrize("N,prec", CASES)
+def test_rstat(runs, N, prec):
+    """rstat_rows against rstat_wg: attempt records, frame records and counters equal, with
+    attempts of one frame that end differently; the uncoded column is the min-sum trace's."""
+    r = runs(N, prec)
+    ctx = r["ctx"]
+    cfg = native.RstatConfig(attempts=ATTEMPTS, precision=PREC[prec][0], **NGDBF)
+    att, frames, counts = {}, {}, {}
+    for opt, kernel in ((0, "rstat_rows"), (1, "rstat_wg")):
+        ctx.reset_options()
+        ctx.set_option("gdbf_kernel", opt)
+        assert ctx.rstat_kernel_info(cfg)["kernel"] == kernel
+        att[kernel], frames[kernel], cnt, _ = ctx.rstat_sim(EBN0, RATE, cfg, SEED, STREAM, FIRST_CW, BATCH)
+        counts[kernel] = cnt.as_array()
+        assert att[kernel].shape == (BATCH, ATTEMPTS)
+        assert cnt.frames == BATCH and cnt.uncoded_bit_err == int(frames[kernel]["uncoded_bit_err"].sum())
+    ctx.reset_options()
+    a = att["rstat_wg"]
+    assert any(len({tuple(x) for x in a[b].tolist()}) > 1 for b in range(BATCH))
+    assert np.array_equal(att["rstat_rows"], att["rstat_wg"])
+    assert np.array_equal(frames["rstat_rows"], frames["rstat_wg"])
+    assert np.array_equal(counts["rstat_rows"], counts["rstat_wg"])
+    assert np.array_equal(frames["rstat_rows"]["uncoded_bit_err"], r["ms_lds"]["fr"]["uncoded_bit_err"])
