@@ -109,14 +109,16 @@ typedef struct {
     int32_t iters;            /* GDBF: iterations run (`it`, decodeGDBF.cpp:399); DD-BMP:
                                * `it` of decodeDDBMP.cpp:230 (a frame that stops inside
                                * iteration index it counts it, one that never stops T);
-                               * min-sum, BP: 0 */
+                               * min-sum, BP: 0, or with cfg.early_stop the s of the
+                               * returned D(s) (see ldpc_decoder_cfg.early_stop) */
 } ldpc_frame_result;
 
 typedef struct {
     int32_t variant;    /* ldpc_variant                                     */
     int32_t precision;  /* ldpc_precision                                   */
-    int32_t T;          /* iterations (num_iterations): fixed, no early stop;
-                         * DD-BMP: the maximum (early stop)                   */
+    int32_t T;          /* iterations (num_iterations): fixed, no early stop
+                         * (early_stop = 1: the maximum); DD-BMP: the maximum
+                         * (it always stops early)                            */
     int32_t quantize;   /* -D quantizeSamples: quantize(y, ymax, 2^qbits)   */
     int32_t saturate;   /* -D saturateSamples: clip at +-ymax               */
     int32_t qbits;      /* Q                                                */
@@ -124,7 +126,18 @@ typedef struct {
     double  alpha;      /* NMS divisor                                      */
     double  delta;      /* OMS offset                                       */
     int32_t schedule;   /* ldpc_schedule (ABI 2)                            */
-    int32_t reserved;   /* 0                                                */
+    int32_t early_stop; /* MS / NMS / OMS / BP, flooding: 0 = T iterations, as the
+                         * reference (decodeMinSum / decodeBP have no early stop);
+                         * 1 = with D(t) what the decoder returns for the frame at
+                         * T = t (decisions, bit_err, uncoded_bit_err, syndrome_fail),
+                         * the frame's result is D(s) for the smallest s in 0..T with
+                         * syndrome_fail == 0 (s = T when there is none): the syndrome
+                         * is checked before every iteration and after the last.
+                         * frames[].iters = s and counts->iters += s. A frame's result
+                         * does not depend on the other frames, the batch size or the
+                         * kernel. LDPC_ERR_UNSUPPORTED with LDPC_LAYERED and with
+                         * LDPC_OPT_KERNEL = 2 (flood); ignored by DD-BMP. The field
+                         * was `reserved` (0) before: same offset, ABI unchanged. */
     double  n0;         /* BP: noise density N0 of the LLR front-end 4*y/N0 (ABI 4);
                          * ldpc_decode_batch needs it > 0, the sim entry points
                          * compute it from Eb/N0 and R (:104)               */
@@ -234,7 +247,7 @@ int  ldpc_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_decoder_
 /* Device time (ms) of the last decode kernel, from HIP events recorded on
  * the launch stream around it. Synchronises that stream. */
 int  ldpc_ctx_last_kernel_ms(ldpc_ctx *ctx, float *ms);
-/* Kernel chosen for a cfg ("rows_pp", "rows_fast", "rows", "lds", "flood",
+/* Kernel chosen for a cfg ("rows_pp", "rows_fast", "rows", "rows_es", "lds", "flood",
  * "global", "layered_*", "bp_*", "ddbmp_rows" / "ddbmp_lds" / "ddbmp_global")
  * and its per-codeword LDS bytes. */
 int  ldpc_ctx_kernel_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, char *name, int name_len,
@@ -245,7 +258,7 @@ int  ldpc_ctx_kernel_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, char *name
  * the fast kernel). Diagnostic of the fast/exact split; synchronises the
  * stream. No reference counterpart (the reference has one exact path). */
 int  ldpc_ctx_redo_count(ldpc_ctx *ctx, int64_t *n);
-/* Shape of the row kernel ("rows"/"rows_fast"/"rows_pp") that decodes cfg, for the
+/* Shape of the row kernel ("rows"/"rows_fast"/"rows_pp"/"rows_es") that decodes cfg, for the
  * on-chip (LDS) roofline model of bench.py: info[10] = {threads per block,
  * rows per thread, bit slots per thread, padded row degree, padded edge slots
  * e_pad, codewords per block, LDS bytes per block, blocks per CU, the low row
@@ -280,7 +293,7 @@ typedef enum {
     LDPC_OPT_LAYERED_LDS_POS = 13, /* global layered kernel: positions kept in LDS + 1 (0 = as many as fit)   */
     LDPC_OPT_LAYERED_ROWS64 = 14,  /* 512-thread global layered kernel, fp64 rows per pass: 1 or 2 (0 = 2)    */
     LDPC_OPT_LAYERED_THREADS = 15, /* global layered kernel threads: 512 or 1024 (0 = 1024)                   */
-    LDPC_OPT_ROWS_BPC = 16,        /* row kernel (k_decode_rows): blocks per CU cap (0 = occupancy)           */
+    LDPC_OPT_ROWS_BPC = 16,        /* row kernel (k_decode_rows, k_rows_es): blocks per CU cap (0 = occupancy) */
     LDPC_OPT_FAST_BPC = 17,        /* rows_fast: blocks per CU cap (0 = occupancy)                            */
     LDPC_OPT_BP_KERNEL = 18,       /* belief propagation: 0 bp_rows when the code fits, 1 the generic kernel  */
     LDPC_OPT_GDBF_KERNEL = 19,     /* GDBF: 0 gdbf_rows when the code and flags fit, 1 the generic kernel     */

@@ -44,7 +44,8 @@ static const char *check_site_name(unsigned s)
         "flood c2v / eref slot", "flood packed-state row", "gdbf_rows bit", "gdbf_rows check term slot",
         "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity",
         "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
-        "hwgdbf noise sample", "rstat decision byte", "rstat check parity"};
+        "hwgdbf noise sample", "rstat decision byte", "rstat check parity", "rows_es gather (app entry)",
+        "rows_es scatter (c2v slot)", "rows_es bit read (c2v slot)", "rows_es app write"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -53,7 +54,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
-                                              check_take_rgdbf, check_take_hwgdbf, check_take_rstat};
+                                              check_take_rgdbf, check_take_hwgdbf, check_take_rstat, check_take_rows_es};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -527,6 +528,13 @@ static int check_cfg(const ldpc_ctx *c, const ldpc_decoder_cfg *cfg)
     if (cfg->schedule == LDPC_LAYERED && !c->has_ls)
         return set_err(LDPC_ERR_UNSUPPORTED, "layered schedule unavailable for this graph (row degree > %d)",
                        ldpc::kPackedMaxDc);
+    if (cfg->early_stop && cfg->variant != LDPC_DDBMP) {   // DD-BMP always stops: the field is not read
+        if (cfg->early_stop != 1) return set_err(LDPC_ERR_INVALID, "early_stop must be 0 or 1");
+        if (cfg->schedule == LDPC_LAYERED)
+            return set_err(LDPC_ERR_UNSUPPORTED, "early_stop is not supported with the layered schedule");
+        if (cfg->variant != LDPC_BP && c->opts.v[LDPC_OPT_KERNEL] == 2)
+            return set_err(LDPC_ERR_UNSUPPORTED, "early_stop is not supported by the flood kernels (LDPC_OPT_KERNEL = 2)");
+    }
     return LDPC_OK;
 }
 
@@ -538,6 +546,7 @@ static void fill_common(ldpc::DecodeArgs &a, ldpc_ctx *c, const ldpc_decoder_cfg
     a.variant = cfg->variant;
     a.quantize = cfg->quantize;
     a.saturate = cfg->saturate;
+    a.early_stop = cfg->variant != LDPC_DDBMP && cfg->early_stop;
     a.ymax = cfg->ymax;
     a.nq = std::pow(2.0, (double)cfg->qbits);   // Nq = pow(2.0, Q) (:121)
     a.alpha = cfg->alpha;
@@ -596,6 +605,12 @@ static ldpc::LaunchPlan build_plan(const ldpc_ctx *c, const ldpc::DecodeArgs &a,
         ldpc::plan_ddbmp(in, p);
     } else if (schedule == LDPC_LAYERED) {
         ldpc::plan_layered(in, p);   // check_cfg: the context has the layered schedule
+    } else if (a.early_stop) {
+        // rows_es -> lds -> global: the fast row kernels, flood and layered never stop early (check_cfg
+        // refuses force == FLOOD)
+        const bool planned = (force == AUTO && ldpc::plan_rows_es(in, p)) ||
+                             ((force == AUTO || force == LDS) && ldpc::plan_lds(in, p));
+        if (!planned) ldpc::plan_global(in, p);
     } else {
         const bool planned = (force == FLOOD && ldpc::plan_flood(in, p)) || (force == AUTO && ldpc::plan_rows(in, p)) ||
                              ((force == AUTO || force == LDS) && ldpc::plan_lds(in, p)) ||
@@ -629,6 +644,7 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
     case Kernel::rows: HIP_TRY(ldpc::launch_rows(p, c->dg, a, c->stream)); break;
     case Kernel::rows_fast: HIP_TRY(ldpc::launch_rows_fast(p, c->dg, a, (unsigned *)c->redo.p, c->stream)); break;
     case Kernel::rows_pp: HIP_TRY(ldpc::launch_rows_pp(p, c->dg, a, (unsigned *)c->redo.p, c->stream)); break;
+    case Kernel::rows_es: HIP_TRY(ldpc::launch_rows_es(p, c->dg, a, c->ticket(), c->stream)); break;
     case Kernel::lds:
     case Kernel::global: HIP_TRY(ldpc::launch_generic(p, c->dg, a, c->gscratch.p, c->stream)); break;
     case Kernel::flood_persistent:
@@ -641,7 +657,9 @@ static int run_kernel(ldpc_ctx *c, ldpc::DecodeArgs a, bool f64, int schedule)
         break;
     case Kernel::bp_rows:
     case Kernel::bp_lds:
-    case Kernel::bp_global: HIP_TRY(ldpc::launch_bp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->stream)); break;
+    case Kernel::bp_global:
+        HIP_TRY(ldpc::launch_bp(p, c->dg, a, f64, c->g->E, c->gscratch.p, c->ticket(), c->stream));
+        break;
     case Kernel::ddbmp_rows:
     case Kernel::ddbmp_lds:
     case Kernel::ddbmp_global:

@@ -14,7 +14,9 @@ void plan_bp(const PlanInput &in, LaunchPlan &p);
 hipError_t bp_math_probe(const double *x, double *t, double *l, int n, hipStream_t s);
 // checked builds (LDPC_CHECK): one out-of-range index on purpose (ldpc_check_selftest)
 hipError_t check_selftest_launch(hipStream_t s);
+// ticket: a word of the context that bp_rows hands codewords out by when a.early_stop is set
+// (the launch clears it)
 hipError_t launch_bp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, bool f64, int E, void *gscratch,
-                     hipStream_t s);
+                     unsigned *ticket, hipStream_t s);
 
 }  // namespace ldpc

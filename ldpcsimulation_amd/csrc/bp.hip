@@ -45,7 +45,11 @@ hipError_t bp_math_probe(const double *x, double *t, double *l, int n, hipStream
 }
 template <typename F> __device__ __forceinline__ F bp_abs(F x) { return x < F(0) ? -x : x; }
 
-template <typename F, int SRC, int DCB>
+// ES (DecodeArgs.early_stop; instantiations of their own, so that the fixed-T kernels keep
+// their code): the syndrome of the decisions is also taken before every iteration (before
+// the first: of d = r, as at T = 0), and the codeword stops with D(it), `it` iterations
+// counted and reported, at the first one that is zero.
+template <typename F, int SRC, int DCB, bool ES>
 __device__ __forceinline__ void bp_codeword(const DecodeArgs &a, const DevGraph &g, int b, F *app, F *yq, F *c2v,
                                             int *red)
 {
@@ -74,7 +78,24 @@ __device__ __forceinline__ void bp_codeword(const DecodeArgs &a, const DevGraph 
     for (int e = tid; e < M * dcs; e += nt) c2v[e] = F(0);   // v2c = yq on the first pass (:307-313)
     __syncthreads();
 
-    for (int it = 0; it < a.T; ++it) {
+    // H * d of the decisions after `done` iterations (d = r when none has run, :404-407)
+    auto syndrome = [&](int done) -> int {
+        int synd = 0;
+        for (int j = tid; j < M; j += nt) {
+            const int deg = g.row_deg[j];
+            const int32_t *rc = g.row_cols + (size_t)j * dcs;
+            int par = 0;
+            for (int k = 0; k < deg; ++k) {
+                const F s = app[rc[k]];
+                par ^= done > 0 ? (s > F(0) ? 0 : 1) : (yq[rc[k]] >= F(0) ? 0 : 1);
+            }
+            synd |= par;
+        }
+        return synd;
+    };
+    int it = 0;
+    for (; it < a.T; ++it) {
+        if (ES && !__syncthreads_or(syndrome(it))) break;   // uniform: D(it) is a codeword
         // ---- check nodes (:353-377) ----
         for (int j = tid; j < M; j += nt) {
             const int deg = g.row_deg[j];
@@ -117,27 +138,18 @@ __device__ __forceinline__ void bp_codeword(const DecodeArgs &a, const DevGraph 
         __syncthreads();
     }
 
-    // ---- decisions (:404-407; d = r when T = 0), error weight, syndrome ----
-    int w = 0, synd = 0;
+    // ---- decisions (:404-407; d = r when no iteration ran), error weight, syndrome ----
+    const int done = ES ? it : a.T;
+    int w = 0;
     for (int v = tid; v < N; v += nt) {
-        const int d = a.T > 0 ? (app[v] > F(0) ? 1 : -1) : (yq[v] >= F(0) ? 1 : -1);
+        const int d = done > 0 ? (app[v] > F(0) ? 1 : -1) : (yq[v] >= F(0) ? 1 : -1);
         const int cv = cvec ? cvec[v] : 1;
         w += (d != cv);
         if (a.d_out) a.d_out[(size_t)b * N + v] = (int8_t)d;
     }
-    for (int j = tid; j < M; j += nt) {
-        const int deg = g.row_deg[j];
-        const int32_t *rc = g.row_cols + (size_t)j * dcs;
-        int par = 0;
-        for (int k = 0; k < deg; ++k) {
-            const F s = app[rc[k]];
-            par ^= a.T > 0 ? (s > F(0) ? 0 : 1) : (yq[rc[k]] >= F(0) ? 0 : 1);
-        }
-        synd |= par;
-    }
-    int sums[3] = {w, unc, synd};
+    int sums[3] = {w, unc, syndrome(done)};
     block_sum_n_t0<3>(sums, red);
-    if (tid == 0) frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
+    if (tid == 0) frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, done, ES ? it : 0);
     __syncthreads();
 }
 
@@ -146,22 +158,22 @@ static size_t bp_state_bytes(const DevGraph &g, size_t fsz)
     return (fsz * (2 * (size_t)g.N + (size_t)g.M * g.dcs) + 255) & ~(size_t)255;
 }
 
-template <typename F, int SRC, int DCB>
+template <typename F, int SRC, int DCB, bool ES>
 __global__ __launch_bounds__(512) void k_bp_lds(DecodeArgs a, DevGraph g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ int red[16 * 4];
     F *app = reinterpret_cast<F *>(smem);
-    bp_codeword<F, SRC, DCB>(a, g, blockIdx.x, app, app + g.N, app + 2 * g.N, red);
+    bp_codeword<F, SRC, DCB, ES>(a, g, blockIdx.x, app, app + g.N, app + 2 * g.N, red);
 }
 
-template <typename F, int SRC, int DCB>
+template <typename F, int SRC, int DCB, bool ES>
 __global__ __launch_bounds__(512) void k_bp_global(DecodeArgs a, DevGraph g, unsigned char *scratch, size_t slot)
 {
     __shared__ int red[16 * 4];
     F *app = reinterpret_cast<F *>(scratch + slot * blockIdx.x);
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x)
-        bp_codeword<F, SRC, DCB>(a, g, b, app, app + g.N, app + 2 * g.N, red);
+        bp_codeword<F, SRC, DCB, ES>(a, g, b, app, app + g.N, app + 2 * g.N, red);
 }
 
 // ---------------------------------------------------------------------
@@ -178,7 +190,13 @@ __global__ __launch_bounds__(512) void k_bp_global(DecodeArgs a, DevGraph g, uns
 //    slots in order (:384-393); padding edges use th = 1.0 in the product
 //    (x * 1.0 == x) and a bit's padding reads a slot holding -0.0 (the exact
 //    identity of +), so every message and sum is the generic kernel's;
-//  * persistent workgroups, two barriers per iteration.
+//  * persistent workgroups, two barriers per iteration;
+//  * ES (DecodeArgs.early_stop, an instantiation of its own): the signs of the app values
+//    the check phase gathers are the syndrome of D(it) (>= before the first iteration,
+//    d = r); a wave with an unsatisfied row raises the double-buffered flag red[4 + (it & 1)]
+//    before the check phase's barrier, every thread reads it after, and the codeword stops
+//    with app = D(it). Codewords then go by ticket (k_ddbmp_rows): blockIdx.x first, then
+//    gridDim.x + atomicAdd(ticket, 1), the next one drawn while the current one decodes.
 // LDPC_BP_KERNEL=generic keeps the one-workgroup-per-codeword kernel.
 // ---------------------------------------------------------------------
 struct BpRowsLayout {
@@ -210,8 +228,9 @@ static bool bp_rows_fits(const DevGraph &g, int E, bool f64)
 #ifndef LDPC_BP_ROWS_WAVES
 #define LDPC_BP_ROWS_WAVES 8   // 512-thread fp32 instance: 64 VGPRs, 4 workgroups per CU (11.9 vs 14.2 ms at 4)
 #endif
-template <typename F, int SRC, int NT>
-__global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVES : 4) void k_bp_rows(DecodeArgs a, DevGraph g, int msg_off, int E)
+template <typename F, int SRC, int NT, bool ES>
+__global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVES : 4) void k_bp_rows(DecodeArgs a, DevGraph g, int msg_off, int E,
+                                                                                                      unsigned *ticket)
 {
     constexpr int DC = 8, RPT = 2;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -270,6 +289,7 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
 #pragma unroll
         for (int q = 0; q < 3; ++q) red[q] = 0;   // block_sum_lds totals
     }
+    [[maybe_unused]] volatile int *fl = red + 4;   // ES: the stop flag; red[6]: the next codeword
     // frame.h reads the frame's fields from a copy: this kernel hands `a` itself to no function, and
     // the fp64 Philox instance (128 VGPRs, 124 bytes spilled) spills 144-148 bytes once it does.
     // For the same reason the y_out store sits in the sample loop in fp64 and after it in fp32
@@ -283,7 +303,9 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
         double sigma;
     } fa = {a.y, a.c, a.cw_table, a.cw_rows, a.seed, a.first_cw, a.stream_id, a.sigma};
 
-    for (int b = blockIdx.x; b < a.batch; b += gridDim.x) {
+    [[maybe_unused]] unsigned nxt = 0;
+    if (ES && tid == 0) nxt = gridDim.x + atomicAdd(ticket, 1u);
+    for (int b = blockIdx.x; b < a.batch;) {
         const int8_t *cvec = frame_codeword<SRC>(fa, b, N);
         // ---- channel + LLR front-end (:184-197), as bp_codeword ----
         int unc = 0;
@@ -311,14 +333,20 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
         for (int r = 0; r < RPT; ++r)
 #pragma unroll
             for (int k = 0; k < DC; ++k) prev[r][k] = F(0);
+        if (ES && tid == 0) {
+            fl[0] = 0;
+            fl[1] = 0;
+        }
         __syncthreads();
 
-        for (int it = 0; it < a.T; ++it) {
+        int it = 0;
+        for (; it < a.T; ++it) {
 #pragma unroll
             for (int r = 0; r < RPT; ++r)
 #pragma unroll
                 for (int k = 0; k < DC / 2; ++k) asm volatile("" : "+v"(rc[r][k]), "+v"(rp[r][k]));
             // ---- check nodes (:353-377) ----
+            [[maybe_unused]] int fail = 0;
             if (LDPC_BP_PRIOBAL) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
             for (int r = 0; r < RPT; ++r) {
@@ -331,8 +359,9 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
                 for (int k = 0; k < DC; ++k) {
                     th[k] = F(1);
                     if (sizeof(F) == 4 || k < wmax[r]) {
-                        F v = app[LDPC_CHK((rc[r][k / 2] >> (16 * (k & 1))) & 0xffffu, (uint32_t)N + 1, CHK_BP_COL)] -
-                              prev[r][k];   // :399
+                        const F s = app[LDPC_CHK((rc[r][k / 2] >> (16 * (k & 1))) & 0xffffu, (uint32_t)N + 1, CHK_BP_COL)];
+                        if (ES && k < rdeg[r]) fail ^= (it > 0 ? (s > F(0) ? 0 : 1) : (s >= F(0) ? 0 : 1)) << r;
+                        F v = s - prev[r][k];   // :399
                         if (bp_abs(v) > maxllr) v = maxllr * (v >= F(0) ? F(1) : F(-1));      // :400-401
                         th[k] = k < rdeg[r] ? bp_tanh(v / F(2)) : F(1);
                     }
@@ -357,7 +386,12 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
                 }
             }
             if (LDPC_BP_PRIOBAL) __builtin_amdgcn_s_setprio(0);
+            if (ES && __builtin_amdgcn_ballot_w64(fail != 0) != 0 && (tid & 63) == 0) fl[it & 1] = 1;
             __syncthreads();
+            if (ES) {
+                if (fl[it & 1] == 0) break;           // uniform over the workgroup: D(it) is a codeword
+                if (tid == 0) fl[(it + 1) & 1] = 0;   // nobody reads or sets it before the next barrier
+            }
             // ---- bit nodes: sum in nlist order (:384-393) ----
             if (own) {
 #pragma unroll
@@ -370,7 +404,8 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
             __syncthreads();
         }
 
-        // ---- decisions (:404-407; d = r when T = 0), error weight, syndrome ----
+        // ---- decisions (:404-407; d = r when no iteration ran), error weight, syndrome ----
+        const bool ran = ES ? it > 0 : a.T > 0;
         int w = 0, synd = 0;
         if (own)
 #pragma unroll
@@ -378,7 +413,7 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
                 const int v = v0 + q;
                 if (v < N) {
                     const F s = app[v];
-                    const int d = a.T > 0 ? (s > F(0) ? 1 : -1) : (s >= F(0) ? 1 : -1);
+                    const int d = ran ? (s > F(0) ? 1 : -1) : (s >= F(0) ? 1 : -1);
                     const int cv = cvec ? cvec[v] : 1;
                     w += (d != cv);
                     if (a.d_out) a.d_out[(size_t)b * N + v] = (int8_t)d;
@@ -391,14 +426,23 @@ __global__ __launch_bounds__(NT, NT == 512 && sizeof(F) == 4 ? LDPC_BP_ROWS_WAVE
             for (int k = 0; k < DC; ++k)
                 if (k < rdeg[r]) {
                     const F s = app[LDPC_CHK((rc[r][k / 2] >> (16 * (k & 1))) & 0xffffu, (uint32_t)N + 1, CHK_BP_COL)];
-                    par ^= a.T > 0 ? (s > F(0) ? 0 : 1) : (s >= F(0) ? 0 : 1);
+                    par ^= ran ? (s > F(0) ? 0 : 1) : (s >= F(0) ? 0 : 1);
                 }
             synd |= par;
         }
         int sums[3] = {w, unc, synd};
         block_sum_lds<3>(sums, red);   // re-zeroed by thread 0; the step's last barrier orders it
-        if (tid == 0) frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
+        if (tid == 0) {
+            frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, ES ? it : a.T, ES ? it : 0);
+            if (ES) red[6] = (int)nxt;
+        }
         __syncthreads();
+        if (ES) {
+            b = red[6];   // rewritten only after the next codeword's barriers
+            if (tid == 0 && b < a.batch) nxt = gridDim.x + atomicAdd(ticket, 1u);
+        } else {
+            b += gridDim.x;
+        }
     }
 }
 
@@ -422,15 +466,15 @@ static bool bp_rows_forced_off() { return opt(LDPC_OPT_BP_KERNEL) == 1; }
 
 constexpr size_t kBpMaxLds = 160 * 1024;
 
-template <typename F, int SRC>
+template <typename F, int SRC, bool ES>
 static const void *bp_fn(const DevGraph &g, Kernel k, int threads)
 {
     if (k == Kernel::bp_rows)
-        return threads == 512 ? (const void *)k_bp_rows<F, SRC, 512> : (const void *)k_bp_rows<F, SRC, 1024>;
+        return threads == 512 ? (const void *)k_bp_rows<F, SRC, 512, ES> : (const void *)k_bp_rows<F, SRC, 1024, ES>;
     const bool lds = k == Kernel::bp_lds;
-    if (g.dcs <= 8) return lds ? (const void *)k_bp_lds<F, SRC, 8> : (const void *)k_bp_global<F, SRC, 8>;
-    if (g.dcs <= 16) return lds ? (const void *)k_bp_lds<F, SRC, 16> : (const void *)k_bp_global<F, SRC, 16>;
-    return lds ? (const void *)k_bp_lds<F, SRC, kBpMaxDc> : (const void *)k_bp_global<F, SRC, kBpMaxDc>;
+    if (g.dcs <= 8) return lds ? (const void *)k_bp_lds<F, SRC, 8, ES> : (const void *)k_bp_global<F, SRC, 8, ES>;
+    if (g.dcs <= 16) return lds ? (const void *)k_bp_lds<F, SRC, 16, ES> : (const void *)k_bp_global<F, SRC, 16, ES>;
+    return lds ? (const void *)k_bp_lds<F, SRC, kBpMaxDc, ES> : (const void *)k_bp_global<F, SRC, kBpMaxDc, ES>;
 }
 
 void plan_bp(const PlanInput &in, LaunchPlan &p)
@@ -456,7 +500,9 @@ void plan_bp(const PlanInput &in, LaunchPlan &p)
         }
     }
     p.fn = for_f_src(in.f64, in.a.src, [&](auto f, auto s) {
-        return bp_fn<typename decltype(f)::type, decltype(s)::value>(g, p.kernel, p.threads);
+        using F = typename decltype(f)::type;
+        constexpr int SRC = decltype(s)::value;
+        return in.a.early_stop ? bp_fn<F, SRC, true>(g, p.kernel, p.threads) : bp_fn<F, SRC, false>(g, p.kernel, p.threads);
     });
     if (p.kernel == Kernel::bp_rows) {   // persistent: what the CU holds
         const int per_cu = std::max(1, occupancy(p.fn, p.threads, p.lds_bytes));
@@ -470,11 +516,16 @@ void plan_bp(const PlanInput &in, LaunchPlan &p)
 }
 
 hipError_t launch_bp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, bool f64, int E, void *gscratch,
-                     hipStream_t s)
+                     unsigned *ticket, hipStream_t s)
 {
     if (p.kernel == Kernel::bp_rows) {
+        if (a.early_stop) {   // codewords by ticket
+            if (!ticket) return hipErrorInvalidValue;
+            const hipError_t e = hipMemsetAsync(ticket, 0, sizeof(unsigned), s);
+            if (e != hipSuccess) return e;
+        }
         int msg_off = bp_rows_layout(g.N, E, f64 ? 8 : 4).msg_off;
-        void *args[] = {(void *)&a, (void *)&g, &msg_off, &E};
+        void *args[] = {(void *)&a, (void *)&g, &msg_off, &E, &ticket};
         return launch_fn(p, args, s);
     }
     unsigned char *gs = (unsigned char *)gscratch;

@@ -45,6 +45,10 @@ enum CheckSite : unsigned {
     CHK_HWGDBF_NOISE,      // hwgdbf: noise sample i + qpointer a bit reads     (< qlen)
     CHK_RSTAT_BIT,         // rstat: decision byte a check gathers (rstat_wg < N, rstat_rows < np)
     CHK_RSTAT_PARITY,      // rstat: parity byte a bit reads / a row writes (rstat_wg < M, rstat_rows < M + 1)
+    CHK_ES_GATHER,         // rows_es: app entry of a check row's edge      (< N + 2)
+    CHK_ES_SCATTER,        // rows_es: c2v slot of a check row's edge       (< e_pad + 64)
+    CHK_ES_BIT_READ,       // rows_es: c2v slot a bit slot reads            (< e_pad + 64)
+    CHK_ES_APP_WRITE,      // rows_es: app entry a bit slot writes          (< N + 2)
     CHK_SITES
 };
 
@@ -109,6 +113,7 @@ hipError_t check_take_ddbmp(CheckRec *out);
 hipError_t check_take_rgdbf(CheckRec *out);
 hipError_t check_take_hwgdbf(CheckRec *out);
 hipError_t check_take_rstat(CheckRec *out);
+hipError_t check_take_rows_es(CheckRec *out);
 #endif
 
 }  // namespace ldpc

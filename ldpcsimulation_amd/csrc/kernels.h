@@ -1,5 +1,5 @@
 // kernels.h -- internal launch interface between api.cpp and the min-sum kernel files
-// (kernels.hip, rows.hip, rows_fast.hip, rows_pp.hip, flood.hip, layered.hip).
+// (kernels.hip, rows.hip, rows_es.hip, rows_fast.hip, rows_pp.hip, flood.hip, layered.hip).
 #pragma once
 #include "options.h"
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@ enum { VARIANT_BP = 3, VARIANT_DDBMP = 4 };   // ldpc_variant LDPC_BP, LDPC_DDBM
 
 struct DecodeArgs {
     int batch, T, variant, quantize, saturate;
+    int early_stop;                 // MS / NMS / OMS / BP: stop at the first t in 0..T whose decisions are a codeword
     double ymax, nq, alpha, delta;
     double n0, max_llr;             // BP front-end: yq = 4*y/n0 clipped to +-max_llr
     // fp32 NMS: q = x*r, q += fma(-q, alpha, x)*r equals x/alpha for every
@@ -36,7 +37,7 @@ struct DecodeArgs {
     double sigma;
     int8_t *d_out;                  // [batch][N] or null
     void *y_out;                    // SRC_PHILOX: channel samples [batch][N] F (pre front-end) or null
-    int4 *frame_res;                // [batch] {bit_err, uncoded, syndrome_fail, iterations (DD-BMP; else 0)} or null
+    int4 *frame_res;                // [batch] {bit_err, uncoded, syndrome_fail, iterations (DD-BMP, early_stop; else 0)} or null
     unsigned long long *counts;     // [6] accumulated
     unsigned long long *hist;       // [N] accumulated (weight w -> hist[w-1])
     unsigned long long *stamps;     // diagnostic builds (-DLDPC_STAMPS): [grid][4] cycle sums, else null
@@ -78,6 +79,7 @@ struct LayerSched {
 // What a plan can launch: one value per kernel family member.
 enum class Kernel {
     rows, rows_fast, rows_pp,           // row graphs (rows.hip, rows_fast.hip, rows_pp.hip)
+    rows_es,                            // row graphs with early termination (rows_es.hip)
     lds, global,                        // one workgroup per codeword (kernels.hip)
     flood_persistent, flood_phase,      // codes beyond LDS (flood.hip); both report "flood"
     layered_lds, layered_global,        // layered schedule (layered.hip)
@@ -90,7 +92,7 @@ enum class Kernel {
 // from it, ldpc_ctx_kernel_info / ldpc_ctx_row_sched_info report it.
 struct LaunchPlan {
     Kernel kernel = Kernel::global;
-    const char *name = "";          // as reported: "rows", "rows_fast", "rows_pp", "lds", "flood", "global", ...
+    const char *name = "";          // as reported: "rows", "rows_fast", "rows_pp", "rows_es", "lds", "flood", "global", ...
     const void *fn = nullptr;       // the instantiation that launches (null: flood_phase, a launch per phase)
     int threads = 0;
     int lds_bytes = 0;              // dynamic LDS per block that holds decoder state, as reported
@@ -147,6 +149,10 @@ hipError_t launch_generic(const LaunchPlan &p, const DevGraph &g, const DecodeAr
 // rows_pp.hip: plan_rows_fast / plan_rows_pp amend the row kernel's plan).
 bool plan_rows(const PlanInput &in, LaunchPlan &p);
 hipError_t launch_rows(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, hipStream_t s);
+// rows_es.hip: the row kernel with early termination (DecodeArgs.early_stop), codewords by
+// ticket (a zeroed word of the context; the launch clears it).
+bool plan_rows_es(const PlanInput &in, LaunchPlan &p);
+hipError_t launch_rows_es(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *ticket, hipStream_t s);
 // flood.hip: codes whose state exceeds LDS (row degree <= kPackedMaxDc), persistent or one
 // launch per phase over an Infinity-Cache-resident set of plan.grid codewords.
 // aux (may be null): a second stream with fork/join events; the resident set is

@@ -27,8 +27,12 @@ namespace ldpc {
 // ---------------------------------------------------------------------
 // One codeword, all T iterations. rows/app/yq may live in LDS or in a
 // per-workgroup global scratch slot; red is LDS.
+// ES (DecodeArgs.early_stop; instantiations of their own, so that the fixed-T kernels keep
+// their code): the syndrome of the decisions is also taken before every iteration, and the
+// codeword stops with D(it), `it` iterations counted and reported, at the first one that
+// is zero (rows_es.hip states the rule).
 // ---------------------------------------------------------------------
-template <typename F, int SRC>
+template <typename F, int SRC, bool ES>
 __device__ __forceinline__ void decode_codeword(const DecodeArgs &a, const DevGraph &g, int b,
                                                 RowState<F> *rows, F *app, F *yq, int *red)
 {
@@ -53,7 +57,21 @@ __device__ __forceinline__ void decode_codeword(const DecodeArgs &a, const DevGr
     __syncthreads();
 
     const F alpha = (F)a.alpha, delta = (F)a.delta;
-    for (int it = 0; it < a.T; ++it) {
+    // H * d of the decisions app holds (complete: a barrier precedes every call)
+    auto syndrome = [&]() -> int {
+        int synd = 0;
+        for (int j = tid; j < M; j += nt) {
+            const int deg = g.row_deg[j];
+            const int32_t *rc = g.row_cols + (size_t)j * g.dcs;
+            int par = 0;
+            for (int k = 0; k < deg; ++k) par ^= (app[rc[k]] > F(0)) ? 0 : 1;
+            synd |= par;
+        }
+        return synd;
+    };
+    int it = 0;
+    for (; it < a.T; ++it) {
+        if (ES && !__syncthreads_or(syndrome())) break;   // uniform: D(it) is a codeword
         // ---- check nodes ----
         for (int j = tid; j < M; j += nt) {
             RowState<F> st = rows[j];
@@ -119,23 +137,15 @@ __device__ __forceinline__ void decode_codeword(const DecodeArgs &a, const DevGr
         w += (d != cv);
         if (a.d_out) a.d_out[(size_t)b * N + v] = (int8_t)d;
     }
-    int synd = 0;
-    for (int j = tid; j < M; j += nt) {
-        const int deg = g.row_deg[j];
-        const int32_t *rc = g.row_cols + (size_t)j * g.dcs;
-        int par = 0;
-        for (int k = 0; k < deg; ++k) par ^= (app[rc[k]] > F(0)) ? 0 : 1;
-        synd |= par;
-    }
-    int sums[3] = {w, unc, synd};
+    int sums[3] = {w, unc, syndrome()};
     block_sum_n_t0<3>(sums, red);
     if (tid == 0)   // the block totals exist in thread 0 only
-        frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, a.T, 0);
+        frame_account(a.counts, a.hist, a.frame_res, b, sums[0], sums[1], sums[2] > 0, ES ? it : a.T, ES ? it : 0);
     __syncthreads();
 }
 
 // State in LDS: one codeword per workgroup, grid = batch.
-template <typename F, int SRC>
+template <typename F, int SRC, bool ES>
 __global__ __launch_bounds__(256) void k_decode_lds(DecodeArgs a, DevGraph g)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -143,13 +153,14 @@ __global__ __launch_bounds__(256) void k_decode_lds(DecodeArgs a, DevGraph g)
     F *app = reinterpret_cast<F *>(smem + sizeof(RowState<F>) * (size_t)g.M);
     F *yq = app + g.N;
     int *red = reinterpret_cast<int *>(yq + g.N);
-    decode_codeword<F, SRC>(a, g, blockIdx.x, rows, app, yq, red);
+    decode_codeword<F, SRC, ES>(a, g, blockIdx.x, rows, app, yq, red);
 }
 
 // Re-decode list of the fast row kernel (rows_fast.hip): redo[0] codewords
 // whose fast-path premise failed, batch indices in redo[1..]; each is decoded
 // from scratch on this exact path (state in LDS), persistent grid. With an
-// empty list every block exits at once.
+// empty list every block exits at once. The fast kernels are not planned with early_stop:
+// this one never stops early.
 template <typename F, int SRC>
 __global__ __launch_bounds__(256) void k_redo(DecodeArgs a, DevGraph g, const unsigned *redo)
 {
@@ -159,12 +170,12 @@ __global__ __launch_bounds__(256) void k_redo(DecodeArgs a, DevGraph g, const un
     F *yq = app + g.N;
     int *red = reinterpret_cast<int *>(yq + g.N);
     const unsigned n = redo[0];
-    for (unsigned i = blockIdx.x; i < n; i += gridDim.x) decode_codeword<F, SRC>(a, g, (int)redo[1 + i], rows, app, yq, red);
+    for (unsigned i = blockIdx.x; i < n; i += gridDim.x) decode_codeword<F, SRC, false>(a, g, (int)redo[1 + i], rows, app, yq, red);
 }
 
 // State in a global scratch slot per workgroup (codes whose state exceeds
 // LDS, e.g. DVB-S2 N=64800): persistent grid, codewords strided.
-template <typename F, int SRC>
+template <typename F, int SRC, bool ES>
 __global__ __launch_bounds__(256) void k_decode_global(DecodeArgs a, DevGraph g, unsigned char *scratch,
                                                        size_t slot_bytes)
 {
@@ -174,7 +185,7 @@ __global__ __launch_bounds__(256) void k_decode_global(DecodeArgs a, DevGraph g,
     F *app = reinterpret_cast<F *>(base + sizeof(RowState<F>) * (size_t)g.M);
     F *yq = app + g.N;
     for (int b = blockIdx.x; b < a.batch; b += gridDim.x)
-        decode_codeword<F, SRC>(a, g, b, rows, app, yq, red);
+        decode_codeword<F, SRC, ES>(a, g, b, rows, app, yq, red);
 }
 
 
@@ -242,7 +253,12 @@ bool plan_lds(const PlanInput &in, LaunchPlan &p)
 {
     const size_t lds = (state_bytes(in.g, in.f64) + 64 + 15) & ~(size_t)15;
     if (lds > kMaxLds) return false;
-    const auto fn = [](auto f, auto s) { return (const void *)k_decode_lds<typename decltype(f)::type, decltype(s)::value>; };
+    const bool es = in.a.early_stop != 0;
+    const auto fn = [es](auto f, auto s) {
+        using F = typename decltype(f)::type;
+        constexpr int SRC = decltype(s)::value;
+        return es ? (const void *)k_decode_lds<F, SRC, true> : (const void *)k_decode_lds<F, SRC, false>;
+    };
     p = LaunchPlan{};
     p.kernel = Kernel::lds;
     p.name = "lds";
@@ -256,7 +272,12 @@ bool plan_lds(const PlanInput &in, LaunchPlan &p)
 
 void plan_global(const PlanInput &in, LaunchPlan &p)
 {
-    const auto fn = [](auto f, auto s) { return (const void *)k_decode_global<typename decltype(f)::type, decltype(s)::value>; };
+    const bool es = in.a.early_stop != 0;
+    const auto fn = [es](auto f, auto s) {
+        using F = typename decltype(f)::type;
+        constexpr int SRC = decltype(s)::value;
+        return es ? (const void *)k_decode_global<F, SRC, true> : (const void *)k_decode_global<F, SRC, false>;
+    };
     p = LaunchPlan{};
     p.kernel = Kernel::global;
     p.name = "global";

@@ -23,58 +23,6 @@ namespace ldpc {
 // =====================================================================
 
 
-// Check node, exact path: the reference's comparisons for any input, incl.
-// infinities and NaN (checkNodeUpdates :410-450, applyNormalization :494-499,
-// applyOffset :503-515). pv[k].v[c]: in = c2v sent last iteration, out = new c2v.
-template <typename F, int C, int DC, typename MT>
-__device__ __forceinline__ void cn_exact(const Pack<F, C> (&xin)[DC], int c, Pack<F, C> (&pv)[DC], MT degmask,
-                                         const DecodeArgs &a, F alpha, F delta)
-{
-    F ax[DC];
-    F mn1 = dinf<F>(), mn2 = dinf<F>();
-    MT sg = 0;
-#pragma unroll
-    for (int k = 0; k < DC; ++k) {
-        const F x = xin[k].v[c] - pv[k].v[c];                       // v2c (:469)
-        sg |= (MT)(!(x >= F(0))) << k;                              // sgn(v2c) (:518-523)
-        ax[k] = dabs(x);
-        // :428-437 -- if (|x| <= m1) {m2 = m1; m1 = |x|} else if (|x| < m2) m2 = |x|
-        // (NaN: no comparison holds and fmin returns the other operand).
-        const bool le = ax[k] <= mn1;
-        mn2 = dmin(mn2, le ? mn1 : ax[k]);
-        mn1 = le ? ax[k] : mn1;
-    }
-    sg &= degmask;
-    const MT eff = (__popcll((unsigned long long)sg) & 1) ? (sg ^ degmask) : sg;   // prod*sgn(v2c_k)
-    // The argmin edge gets m2, every other edge m1 (:444-447). |x_k| == m1
-    // identifies it: on a tie m2 == m1, so which tied edge is "argmin" does not matter.
-    if (a.variant != V_OMS) {
-        F M1 = mn1, M2 = mn2;
-        if (a.variant == V_NMS) {
-            M1 = nms_div<F>(mn1, alpha, a);
-            M2 = nms_div<F>(mn2, alpha, a);
-        }
-#pragma unroll
-        for (int k = 0; k < DC; ++k) {
-            const F mag = (ax[k] == mn1) ? M2 : M1;
-            pv[k].v[c] = ((eff >> k) & 1u) ? -mag : mag;
-        }
-    } else {
-        const F t1 = mn1 - delta, t2 = mn2 - delta;
-        const bool p1 = t1 > F(0), p2 = t2 > F(0);
-        const F M1 = p1 ? t1 : F(0), M2 = p2 ? t2 : F(0);
-        // sgn(c2v) maps -0.0 to +1 and a zeroed message is +0
-        const MT e1 = (!p1 || mn1 == F(0)) ? (MT)0 : eff;
-        const MT e2 = (!p2 || mn2 == F(0)) ? (MT)0 : eff;
-#pragma unroll
-        for (int k = 0; k < DC; ++k) {
-            const bool ism = ax[k] == mn1;
-            const F mag = ism ? M2 : M1;
-            pv[k].v[c] = (((ism ? e2 : e1) >> k) & 1u) ? -mag : mag;
-        }
-    }
-}
-
 template <int DC, int C, int DCA = DC, bool PK = false>
 __device__ __forceinline__ bool cn_fast(const Pack<double, C> (&)[DCA], Pack<double, C> (&)[DCA], bool, float, float)
 {

@@ -83,7 +83,7 @@ class _Cfg(C.Structure):
     _fields_ = [("variant", C.c_int32), ("precision", C.c_int32), ("T", C.c_int32),
                 ("quantize", C.c_int32), ("saturate", C.c_int32), ("qbits", C.c_int32),
                 ("ymax", C.c_double), ("alpha", C.c_double), ("delta", C.c_double),
-                ("schedule", C.c_int32), ("reserved", C.c_int32), ("n0", C.c_double), ("max_llr", C.c_double)]
+                ("schedule", C.c_int32), ("early_stop", C.c_int32), ("n0", C.c_double), ("max_llr", C.c_double)]
 
 
 GDBF_NOISE, GDBF_ADAPT, GDBF_WEIGHT, GDBF_SMOOTH, GDBF_SATURATE, GDBF_QUANTIZE = 1, 2, 4, 8, 16, 32
@@ -239,7 +239,7 @@ def rgdbf_smoothing_used(iters, T: int, maxphase: int, windowsize: int):
 class DecoderConfig:
     """Runtime form of the reference's compile-time decoder switches."""
     variant: int = MS            # MS | NMS (-D normalizedMS) | OMS (-D offsetMS) | BP | DDBMP (decodeDDBMP.cpp)
-    T: int = 10                  # iterations (fixed, no early termination; DDBMP: the maximum)
+    T: int = 10                  # iterations (fixed; the maximum with early_stop and for DDBMP)
     precision: int = F64         # F64 = the reference's double (default) | F32 throughput path (opt-in)
     alpha: float = 1.0           # NMS divisor
     delta: float = 0.0           # OMS offset
@@ -250,10 +250,14 @@ class DecoderConfig:
     schedule: int = FLOODING     # FLOODING (the reference's) | LAYERED (row-serial, config 3)
     n0: float = 0.0              # BP (variant BP): N0 of the LLR front-end 4*y/N0 (decode only)
     max_llr: float = 0.0         # BP: MAXLLR (0 = the reference's 20)
+    # MS / NMS / OMS / BP, flooding: stop a frame at the first t in 0..T whose decisions are a codeword and
+    # return what T = t returns; frames["iters"] = t (include/ldpc_hip.h ldpc_decoder_cfg.early_stop)
+    early_stop: bool = False
 
     def _c(self) -> _Cfg:
         return _Cfg(self.variant, self.precision, self.T, int(self.quantize), int(self.saturate),
-                    self.qbits, self.ymax, self.alpha, self.delta, self.schedule, 0, self.n0, self.max_llr)
+                    self.qbits, self.ymax, self.alpha, self.delta, self.schedule, int(self.early_stop), self.n0,
+                    self.max_llr)
 
 
 class _EmsCfg(C.Structure):

@@ -14,6 +14,8 @@ line for each point.
     # BASELINE config 3: DVB-S2 N=64800 R1/2, layered NMS, SNR sweep over 8 GPUs
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m ldpcsimulation_amd.sweep dvbs2_1_2.alist \\
         --rate 0.5 --snr 0.8 0.9 1.0 1.1 -T 50 --variant nms --alpha 1.25 --schedule layered --batch 2048
+    # early termination (no reference counterpart): every frame stops at its first codeword, avgIt is the true mean
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 2.5 3.0 -T 50 --variant nms --alpha 1.25 --early-stop
     # belief propagation (decodeBP: its stop rule 200 bit / 20|10|5 frame errors)
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 50 --variant bp
     # BASELINE config 5: GF(16) EMS on an NB alist (SystemC/NB-LDPC format), early stop
@@ -101,6 +103,10 @@ def parse(argv=None):
     p.add_argument("--nm", type=int, default=16, help="EMS message truncation")
     p.add_argument("--offset", type=float, default=0.0, help="EMS fill offset")
     p.add_argument("--no-early-stop", action="store_true", help="EMS: always run T iterations")
+    p.add_argument("--early-stop", action="store_true",
+                   help="--variant ms / nms / oms / bp, flooding: stop a frame at the first iteration count whose "
+                        "decisions are a codeword (T is the maximum; avgIt becomes the true mean); the other "
+                        "decoders always stop early and ignore it")
     p.add_argument("--max-frames", type=int, default=None)
     p.add_argument("--codewords", help="codeword file ('0'/'1' lines), as the reference's optional argument")
     p.add_argument("--log", "--log-file", dest="log",
@@ -119,6 +125,8 @@ def parse(argv=None):
                    help="seconds between checkpoint records (0 = after every round); each record "
                         "all-reduces the point's error-weight histogram")
     a = p.parse_args(argv)
+    if a.early_stop and a.schedule == "layered":
+        p.error("--early-stop is not supported with --schedule layered")
     gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
     if a.hwgdbf:
         if a.gdbf or a.ems or a.schedule != "flooding" or a.variant != "ms":
@@ -162,12 +170,20 @@ def _checkpoint_config(a) -> dict:
         ddbmp = {"gdbf": a.gdbf, **_gdbf_settings(a)}
     if getattr(a, "hwgdbf", False):   # likewise
         ddbmp = {"hwgdbf": True, **_hwgdbf_settings(a)}
+    if _min_sum_early_stop(a):   # likewise (the "early_stop" key below is the EMS setting)
+        ddbmp = {**ddbmp, "min_sum_early_stop": True}
     return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
             "snr": list(a.snr), "T": a.iterations, "variant": a.variant, "alpha": a.alpha, "delta": a.delta,
             "quantize": a.quantize, "saturate": a.saturate, "precision": a.precision, "schedule": a.schedule,
             "min_bit_errors": a.min_bit_errors, "min_frame_errors": a.min_frame_errors, "max_frames": a.max_frames,
             "codewords_md5": checkpoint.file_digest(a.codewords), "ems": a.ems, "nm": a.nm, "offset": a.offset,
             "early_stop": not a.no_early_stop}
+
+
+def _min_sum_early_stop(a) -> bool:
+    """--early-stop where it means something: the min-sum variants and BP (the other families always stop)."""
+    return bool(getattr(a, "early_stop", False)) and not (a.ems or getattr(a, "gdbf", None) or getattr(a, "hwgdbf", False)) \
+        and a.variant in ("ms", "nms", "oms", "bp")
 
 
 def _gdbf_settings(a) -> dict:
@@ -250,7 +266,9 @@ def main(argv=None) -> int:
         return _gdbf_sweep(a, seed, world, rank, device, ck)
     cfg = native.DecoderConfig(variant=VARIANTS[a.variant], T=a.iterations, alpha=a.alpha, delta=a.delta,
                                precision=native.F64 if a.precision == "f64" else native.F32,
-                               schedule=native.LAYERED if a.schedule == "layered" else native.FLOODING)
+                               schedule=native.LAYERED if a.schedule == "layered" else native.FLOODING,
+                               early_stop=_min_sum_early_stop(a))
+    stops = a.variant == "ddbmp" or cfg.early_stop   # early stop: frames report their iterations
     extra = []
     if a.quantize:
         cfg.quantize, cfg.ymax, cfg.qbits = True, float(a.quantize[0]), int(a.quantize[1])
@@ -287,7 +305,7 @@ def main(argv=None) -> int:
         t0 = time.perf_counter()
         res = sim.simulate_point(run_batch, g.N, a.iterations, snr, a.batch, a.min_bit_errors,
                                  min_fe, a.max_frames, device=device, launcher=launcher, first_round=a.first_round,
-                                 iters_in_frames=a.variant == "ddbmp",   # early stop: frames report their `it`
+                                 iters_in_frames=stops,
                                  resume=resume, on_round=on_round,
                                  on_round_interval=a.checkpoint_interval)
         dt = time.perf_counter() - t0
@@ -295,7 +313,7 @@ def main(argv=None) -> int:
         ran = c["frames"] - (int(resume.acc[3]) if resume else 0)   # frames counted by this run
         return res, res.log_line(a.alist, extra), {
             "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, "seconds": dt,
-            **({"avg_iters": res.avg_iters} if a.variant == "ddbmp" else {}),
+            **({"avg_iters": res.avg_iters} if stops else {}),
             "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None,
             "n_gpus": world, "wilson95": sim.wilson_interval(c["frame_err"], c["frames"]),
             "precision": a.precision, "schedule": a.schedule, "variant": a.variant,
