@@ -268,6 +268,14 @@ int  ldpc_ctx_redo_count(ldpc_ctx *ctx, int64_t *n);
  * call. No reference counterpart (diagnostic of decodeMinSum.cpp:247-263's
  * replacement). */
 int  ldpc_ctx_row_sched_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t *info);
+/* The in-register bits of the ping-pong kernel for cfg: degree-2 bits whose two check rows
+ * are held by one check thread never pass through LDS. info[4] = {in-register bits,
+ * check-node edge slots that pass through LDS per codeword-iteration, padded bit-slot edges
+ * the bit role walks, bit slots per thread}. Without such bits (a code with no pair,
+ * fp32 pairs, LDPC_OPT_PP_SLOTS 1 or 2) info[0] is 0 and the rest describes ldpc_ctx_row_sched_info's
+ * schedule. LDPC_ERR_UNSUPPORTED when the kernel that decodes cfg is not "rows_pp". Host-only.
+ * No reference counterpart. */
+int  ldpc_ctx_pp_inreg_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t *info);
 
 /* ---- kernel-selection options (ABI 10) ------------------------------- */
 /* The library picks the kernel for a cfg by itself (the reference fixes its
@@ -279,7 +287,9 @@ int  ldpc_ctx_row_sched_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t
 typedef enum {
     LDPC_OPT_ROWS64 = 1,           /* fp64 row graphs: 0 ping-pong (rows_pp), 1 rows_fast, 2 the row kernel   */
     LDPC_OPT_ROWS32 = 2,           /* fp32 MS / NMS row graphs: 0 rows_pp pairs, 1 rows_fast pairs, 2 the row kernel */
-    LDPC_OPT_PP_SLOTS = 3,         /* rows_pp row slots: 0 degree-aware (when the code admits them), 1 plain  */
+    LDPC_OPT_PP_SLOTS = 3,         /* rows_pp row slots: 0 degree-aware (when the code admits them) with the   */
+                                   /* paired rows' degree-2 bits in registers (when it has pairs), 1 plain,   */
+                                   /* 2 degree-aware with every bit in LDS                                    */
     LDPC_OPT_KERNEL = 4,           /* generic kernel: 0 auto, 1 lds, 2 flood (persistent), 3 global           */
     LDPC_OPT_FLOOD_MODE = 5,       /* codes beyond LDS: 0 one launch per phase, 1 the persistent kernel       */
     LDPC_OPT_FLOOD_MSG = 6,        /* phase flooding messages: 0 packed row state, 1 the c2v array            */

@@ -46,6 +46,22 @@ BASE_R12_Z27 = [
     [25, -1, 8, -1, 23, 18, -1, 14, 9, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0],
     [3, -1, -1, -1, 16, -1, -1, 2, 25, 5, -1, -1, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0],
 ]
+# N = 1296 (Z = 54): full rank, girth >= 6 and the degree profile of the other two
+# (tests/test_pp_pairs_host.py pairs its rows).
+BASE_R12_Z54 = [
+    [40, -1, -1, -1, 22, -1, 49, 23, 43, -1, -1, -1, 1, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1],
+    [50, 1, -1, -1, 48, 35, -1, -1, 13, -1, 30, -1, -1, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1, -1],
+    [39, 50, -1, -1, 4, -1, 2, -1, -1, -1, -1, 49, -1, -1, 0, 0, -1, -1, -1, -1, -1, -1, -1, -1],
+    [33, -1, -1, 38, 37, -1, -1, 4, 1, -1, -1, -1, -1, -1, -1, 0, 0, -1, -1, -1, -1, -1, -1, -1],
+    [45, -1, -1, -1, 0, 22, -1, -1, 20, 42, -1, -1, -1, -1, -1, -1, 0, 0, -1, -1, -1, -1, -1, -1],
+    [51, -1, -1, 48, 35, -1, -1, -1, 44, -1, 18, -1, -1, -1, -1, -1, -1, 0, 0, -1, -1, -1, -1, -1],
+    [47, 11, -1, -1, -1, 17, -1, -1, 51, -1, -1, -1, 0, -1, -1, -1, -1, -1, 0, 0, -1, -1, -1, -1],
+    [5, -1, 25, -1, 6, -1, 45, -1, 13, 40, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0, -1, -1, -1],
+    [33, -1, -1, 34, 24, -1, -1, -1, 23, -1, -1, 46, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0, -1, -1],
+    [1, -1, 27, -1, 1, -1, -1, -1, 38, -1, 44, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0, -1],
+    [-1, 18, -1, -1, 23, -1, -1, 8, 0, 35, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0, 0],
+    [49, -1, 17, -1, 30, -1, -1, -1, 34, -1, -1, 19, 1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, 0],
+]
 # md5 of the zero-padded alist of the N=1944 code.
 MD5_80211N_1944 = "6e7b47f79e731d594830a1ba2096f419"
 
@@ -99,9 +115,9 @@ def expand_qc(base: Sequence[Sequence[int]], Z: int, shift: str = "right") -> Pa
 
 
 def ieee80211n_r12(Z: int = 81, shift: str = "right") -> ParityCheck:
-    base = {81: BASE_R12_Z81, 27: BASE_R12_Z27}.get(Z)
+    base = {81: BASE_R12_Z81, 54: BASE_R12_Z54, 27: BASE_R12_Z27}.get(Z)
     if base is None:
-        raise ValueError("Z must be 27 or 81")
+        raise ValueError("Z must be 27, 54 or 81")
     return expand_qc(base, Z, shift)
 
 

@@ -83,6 +83,9 @@ struct ldpc_ctx : CtxCore {
     bool has_rs_pp = false;                               // the ping-pong kernel's degree-aware row slots
     ldpc::RowSched rs_pp{};
     DevBuf sched_pp;
+    bool has_rs_ppi = false;                              // its in-register schedule (the code has row pairs)
+    ldpc::RowSched rs_ppi{};
+    DevBuf sched_ppi;
     bool has_fs = false;
     ldpc::FloodSched fs{};
     DevBuf fsched;                                        // flood kernel schedule (codes beyond LDS)
@@ -113,7 +116,7 @@ bool option_value_ok(int option, int v)
     switch (option) {
     case LDPC_OPT_ROWS64:
     case LDPC_OPT_ROWS32: return v >= 0 && v <= 2;
-    case LDPC_OPT_PP_SLOTS:
+    case LDPC_OPT_PP_SLOTS: return v >= 0 && v <= 2;
     case LDPC_OPT_FLOOD_MODE:
     case LDPC_OPT_FLOOD_MSG:
     case LDPC_OPT_BP_KERNEL:
@@ -154,16 +157,18 @@ static hipError_t upload_graph(const ldpc_graph &g, DevBuf &buf, ldpc::DevGraph 
     return hipSuccess;
 }
 
-static hipError_t upload_row_sched(const ldpc::RowSchedule &hs, DevBuf &buf, ldpc::RowSched &rs)
+// pair_flags (graph.h build_pp_inreg_schedule): the in-register schedule's, else null.
+static hipError_t upload_row_sched(const ldpc::RowSchedule &hs, DevBuf &buf, ldpc::RowSched &rs,
+                                   const std::vector<uint8_t> *pair_flags = nullptr)
 {
     Blob b(256);
     const size_t o_cc = b.add(hs.cn_cols), o_cp = b.add(hs.cn_pos), o_cd = b.add(hs.cn_deg), o_vc = b.add(hs.vn_col),
-                 o_vi = b.add(hs.vn_info);
+                 o_vi = b.add(hs.vn_info), o_pf = pair_flags ? b.add(*pair_flags) : 0;
     const hipError_t e = upload(b, buf);
     if (e != hipSuccess) return e;
     rs = {hs.threads, hs.cpt, hs.dc, hs.e_pad, hs.rpt, hs.dc_low, section<uint16_t>(buf, o_cc),
           section<uint16_t>(buf, o_cp), section<uint8_t>(buf, o_cd), section<uint16_t>(buf, o_vc),
-          section<uint32_t>(buf, o_vi)};
+          section<uint32_t>(buf, o_vi), pair_flags ? section<uint8_t>(buf, o_pf) : nullptr, hs.e_pad, 0, 0};
     return hipSuccess;
 }
 
@@ -396,7 +401,7 @@ static void ctx_free(ldpc_ctx *c)
 {
     if (!c) return;
     c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
-                &c->sched, &c->sched_pp, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
+                &c->sched, &c->sched_pp, &c->sched_ppi, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
                 &c->hw_ptr_stage, &c->hw_it_stage, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
                 &c->rs_tr_stage[2], &c->rs_tr_stage[3]});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
@@ -441,6 +446,25 @@ static int ctx_init(ldpc_ctx *c, int device, const ldpc_graph *g, int max_batch)
             hp.dc_low = 7;
             HIP_TRY(upload_row_sched(hp, c->sched_pp, c->rs_pp));
             c->has_rs_pp = true;
+            // and its in-register variant where a check thread can hold both rows of a degree-2 bit
+            ldpc::PPPairing pr;
+            ldpc::RowSchedule hi;
+            std::vector<uint8_t> flags;
+            if (ldpc::pp_pair_rows(*g, threads, 7, dc, pr) &&
+                ((LDPC_PP_INREG_CPT == 3 && ldpc::build_pp_inreg_schedule(*g, threads, 3, dc, 7, pr, hi, flags).empty()) ||
+                 ldpc::build_pp_inreg_schedule(*g, threads, cpt, dc, 7, pr, hi, flags).empty()) &&
+                hi.e_pad <= hp.e_pad) {
+                const int e_used = hi.e_pad;
+                hi.e_pad = hp.e_pad;   // the split schedule's LDS partition; the smaller c2v area lies inside it
+                HIP_TRY(upload_row_sched(hi, c->sched_ppi, c->rs_ppi, &flags));
+                c->rs_ppi.e_used = e_used;
+                c->rs_ppi.n_inreg = pr.pairs;
+                int pure = 0;
+                for (int w = 0; w < threads / 64; ++w) pure += flags[(size_t)threads + w];
+                // a wave without LDS at its last positions issues two edge slots less per lane
+                c->rs_ppi.lds_edge_slots = (threads + threads / 2) * 7 + (threads / 2) * dc - pure * 64 * 2;
+                c->has_rs_ppi = true;
+            }
         }
     }
     // Flood schedule (global-memory kernel for codes whose state exceeds LDS; also
@@ -596,7 +620,8 @@ static ldpc::LaunchPlan build_plan(const ldpc_ctx *c, const ldpc::DecodeArgs &a,
     enum { AUTO = 0, LDS = 1, FLOOD = 2, GLOBAL = 3 };   // values of LDPC_OPT_KERNEL
     const ldpc::OptScope os(c->opts);
     const ldpc::PlanInput in{c->dg, c->g->E, c->has_rs ? &c->rs : nullptr, c->has_rs_pp ? &c->rs_pp : nullptr,
-                             c->has_fs ? &c->fs : nullptr, c->has_ls ? &c->ls : nullptr, c->num_cus, a, f64, c->g->maxdv};
+                             c->has_fs ? &c->fs : nullptr, c->has_ls ? &c->ls : nullptr, c->num_cus, a, f64, c->g->maxdv,
+                             c->has_rs_ppi ? &c->rs_ppi : nullptr};
     const int force = c->opts.v[LDPC_OPT_KERNEL];
     ldpc::LaunchPlan p;
     if (a.variant == ldpc::VARIANT_BP) {
@@ -833,6 +858,23 @@ int ldpc_ctx_row_sched_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *i
     // node, the other row-1 slots a dc-edge one
     info[9] = rs.dc_low ? (rs.threads + rs.threads / 2) * rs.dc_low + (rs.threads / 2) * rs.dc
                         : rs.threads * rs.rpt * rs.dc;
+    return LDPC_OK;
+}
+
+int ldpc_ctx_pp_inreg_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *info)
+{
+    if (!info) return set_err(LDPC_ERR_INVALID, "null argument");
+    ldpc::LaunchPlan p;
+    RC_TRY(info_plan(c, cfg, p));
+    if (p.kernel != ldpc::Kernel::rows_pp || !p.rs)
+        return set_err(LDPC_ERR_UNSUPPORTED, "the ping-pong kernel does not decode this cfg (kernel %s)", p.name);
+    int32_t rsi[10];
+    RC_TRY(ldpc_ctx_row_sched_info(c, cfg, rsi));
+    const ldpc::RowSched *ri = p.rs_inreg;
+    info[0] = ri ? ri->n_inreg : 0;
+    info[1] = ri ? ri->lds_edge_slots : rsi[9];
+    info[2] = ri ? ri->e_used : p.rs->e_pad;
+    info[3] = ri ? ri->cpt : p.rs->cpt;
     return LDPC_OK;
 }
 

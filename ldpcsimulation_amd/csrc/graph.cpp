@@ -109,11 +109,11 @@ std::vector<int> pp_row_slots(const ldpc_graph &g, int threads, int dc_low)
 }
 
 std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc, int rpt, RowSchedule &s,
-                               const std::vector<int> *row_of_slot)
+                               const std::vector<int> *row_of_slot, const std::vector<uint8_t> *skip_bit)
 {
+    if (skip_bit && skip_bit->size() != (size_t)g.N) return "bit skip map has the wrong size";
     if (threads % 64 || (long)threads * rpt < g.M) return "rows exceed threads";
     if (row_of_slot && row_of_slot->size() != (size_t)threads * rpt) return "row slot map has the wrong size";
-    if ((long)threads * cpt < g.N) return "bits exceed slots";
     if (g.maxdc > dc) return "row degree exceeds kernel bound";
     if (g.N > 65534) return "N exceeds 16-bit schedule";
     s = RowSchedule();
@@ -123,13 +123,17 @@ std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc
     s.rpt = rpt;
     const int rows = threads * rpt;
     // Stable sort of columns by decreasing degree -> slot order.
-    std::vector<int> order(g.N);
-    for (int i = 0; i < g.N; ++i) order[i] = i;
+    std::vector<int> order;
+    order.reserve(g.N);
+    for (int i = 0; i < g.N; ++i)
+        if (!skip_bit || !(*skip_bit)[i]) order.push_back(i);
+    const int NB = (int)order.size();   // bits with a bit slot
+    if ((long)threads * cpt < NB) return "bits exceed slots";
     std::stable_sort(order.begin(), order.end(),
                      [&](int a, int b) { return g.col_deg[a] > g.col_deg[b]; });
     const int nslots = threads * cpt;
     const int waves = threads / 64;
-    const int ngroups = (g.N + 63) / 64;
+    const int ngroups = (NB + 63) / 64;
     if (ngroups > waves * cpt) return "bits exceed slots";
     // Degree of each 64-column group (columns in decreasing-degree order) and
     // the base of its c2v block: edge kc of the group's lane l is at gbase + kc*64 + l.
@@ -137,7 +141,7 @@ std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc
     for (int grp = 0; grp < ngroups; ++grp) {
         for (int l = 0; l < 64; ++l) {
             const int slot = grp * 64 + l;
-            if (slot < g.N) gdeg[grp] = std::max(gdeg[grp], (int)g.col_deg[order[slot]]);
+            if (slot < NB) gdeg[grp] = std::max(gdeg[grp], (int)g.col_deg[order[slot]]);
         }
         gbase[grp + 1] = gbase[grp] + 64 * gdeg[grp];
     }
@@ -183,7 +187,7 @@ std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc
             const int slot = grp * 64 + l;
             const int t = gw[grp] * 64 + l;
             const size_t idx = (size_t)t * cpt + gi[grp];   // thread-major: a thread's slots are contiguous
-            const int v = slot < g.N ? order[slot] : -1;
+            const int v = slot < NB ? order[slot] : -1;
             const int d = v >= 0 ? g.col_deg[v] : 0;
             s.vn_col[idx] = v >= 0 ? (uint16_t)v : (uint16_t)0xffff;
             s.vn_info[idx] = (uint32_t)(gbase[grp] + l) | ((uint32_t)d << 16) | ((uint32_t)gdeg[grp] << 24);
@@ -199,6 +203,153 @@ std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc
         for (int i = 1; i < cpt; ++i)
             if ((s.vn_info[(size_t)t * cpt + i] >> 24) > (s.vn_info[(size_t)t * cpt + i - 1] >> 24))
                 return "internal: bit slots not in non-increasing degree";
+    return "";
+}
+
+bool pp_pair_rows(const ldpc_graph &g, int threads, int dc_low, int dc, PPPairing &out)
+{
+    out = PPPairing();
+    const int half = threads / 2, M = g.M;
+    if (threads % 128 || M > 2 * threads || g.maxdc > dc) return false;
+    // the row graph of the degree-2 bits: per row its (bit, other row) edges in bit order
+    struct Link { int bit, to; };
+    std::vector<std::vector<Link>> adj(M);
+    for (int v = 0; v < g.N; ++v) {
+        if (g.col_deg[v] != 2) continue;
+        const int a = (int)(g.col_refs[g.col_ptr[v]] >> kRefShift), b = (int)(g.col_refs[g.col_ptr[v] + 1] >> kRefShift);
+        if (a == b) continue;
+        adj[a].push_back({v, b});
+        adj[b].push_back({v, a});
+    }
+    // greedy matching along walks that start at the path ends (rows with one such bit),
+    // then anywhere: on a path it pairs rows (0,1), (2,3), ... from the end, which is maximum
+    std::vector<int> mate(M, -1), mbit(M, -1);
+    std::vector<char> used(g.N, 0);
+    auto pairable = [&](int a, int b) {
+        return a != b && mate[a] < 0 && mate[b] < 0 && (g.row_deg[a] <= dc_low || g.row_deg[b] <= dc_low);
+    };
+    auto walk = [&](int start) {
+        for (int cur = start;;) {
+            int nxt = -1, bit = -1;
+            for (const Link &l : adj[cur])
+                if (!used[l.bit]) { nxt = l.to; bit = l.bit; break; }
+            if (nxt < 0) return;
+            used[bit] = 1;
+            if (pairable(cur, nxt)) {
+                mate[cur] = nxt;
+                mate[nxt] = cur;
+                mbit[cur] = mbit[nxt] = bit;
+            }
+            cur = nxt;
+        }
+    };
+    for (int j = 0; j < M; ++j)
+        if (adj[j].size() == 1) walk(j);
+    for (int j = 0; j < M; ++j) walk(j);
+    // pairs in order of their lower row (quasi-cyclic neighbours stay lane neighbours), as
+    // (first, second) rows of the bit's nlist
+    struct Pair { int first, second, bit; };
+    std::vector<Pair> low, high;   // both rows of degree <= dc_low / one row above it
+    for (int j = 0; j < M; ++j) {
+        if (mate[j] < j) continue;   // unmatched (-1) or listed at its lower row
+        const int v = mbit[j], a = (int)(g.col_refs[g.col_ptr[v]] >> kRefShift);
+        const Pair p{a, a == j ? mate[j] : j, v};
+        (g.row_deg[p.first] <= dc_low && g.row_deg[p.second] <= dc_low ? low : high).push_back(p);
+    }
+    out.row_of_slot.assign(2 * (size_t)threads, -1);
+    out.bit_of_thread.assign(threads, -1);
+    out.first_r.assign(threads, 0);
+    std::vector<char> placed(M, 0);
+    int t_old = 0, t_young = half;
+    auto put = [&](int t, const Pair &p, bool swap) {   // swap: the first row at r = 1
+        out.row_of_slot[t] = swap ? p.second : p.first;
+        out.row_of_slot[threads + t] = swap ? p.first : p.second;
+        out.bit_of_thread[t] = p.bit;
+        out.first_r[t] = swap ? 1 : 0;
+        placed[p.first] = placed[p.second] = 1;
+        ++out.pairs;
+    };
+    for (const Pair &p : high)   // the row above dc_low goes to r = 1 of a thread < half
+        if (t_old < half) put(t_old++, p, g.row_deg[p.first] > dc_low);
+    for (const Pair &p : low) {
+        if (t_young < threads) put(t_young++, p, false);
+        else if (t_old < half) put(t_old++, p, false);
+    }
+    if (!out.pairs) {
+        out = PPPairing();
+        return false;
+    }
+    // rows without a partner (or whose pair found no thread): pp_row_slots' fill of what is left
+    std::vector<int> capped, open, rest;
+    for (int t = 0; t < threads; ++t)
+        if (out.bit_of_thread[t] < 0) capped.push_back(t);
+    for (int t = half; t < threads; ++t)
+        if (out.bit_of_thread[t] < 0) capped.push_back(threads + t);
+    for (int t = 0; t < half; ++t)
+        if (out.bit_of_thread[t] < 0) open.push_back(threads + t);
+    size_t nc = 0, no = 0;
+    for (int j = 0; j < M; ++j) {
+        if (placed[j]) continue;
+        if (g.row_deg[j] <= dc_low && nc < capped.size()) out.row_of_slot[capped[nc++]] = j;
+        else rest.push_back(j);
+    }
+    if (rest.size() > open.size()) {
+        out = PPPairing();
+        return false;
+    }
+    for (int j : rest) out.row_of_slot[open[no++]] = j;
+    return true;
+}
+
+std::string build_pp_inreg_schedule(const ldpc_graph &g, int threads, int cpt, int dc, int dc_low,
+                                    const PPPairing &pr, RowSchedule &s, std::vector<uint8_t> &pair_flags)
+{
+    if (pr.row_of_slot.size() != 2 * (size_t)threads || pr.bit_of_thread.size() != (size_t)threads ||
+        pr.first_r.size() != (size_t)threads || dc_low < 1 || dc_low > dc)
+        return "pairing has the wrong size";
+    std::vector<uint8_t> skip(g.N, 0);
+    for (int t = 0; t < threads; ++t) {
+        const int v = pr.bit_of_thread[t];
+        if (v < 0) continue;
+        if (v >= g.N || g.col_deg[v] != 2 || skip[v]) return "pairing names a bit twice or one of degree != 2";
+        skip[v] = 1;
+    }
+    const std::string err = build_row_schedule(g, threads, cpt, dc, 2, s, &pr.row_of_slot, &skip);
+    if (!err.empty()) return err;
+    s.dc_low = dc_low;
+    const int half = threads / 2, waves = threads / 64;
+    pair_flags.assign((size_t)threads + waves, 0);
+    for (int w = 0; w < waves; ++w) pair_flags[threads + w] = 1;
+    for (int t = 0; t < threads; ++t) {
+        const int v = pr.bit_of_thread[t];
+        for (int r = 0; r < 2; ++r) {
+            const int slot = r * threads + t, last = (r == 1 && t < half ? dc : dc_low) - 1;
+            uint16_t *cols = &s.cn_cols[(size_t)slot * dc], *pos = &s.cn_pos[(size_t)slot * dc];
+            const int d = s.cn_deg[slot];
+            if (d > last + 1) return "row slot exceeds its check node";
+            if (v < 0) {   // no pair: a real edge at the last position needs LDS
+                if (d == last + 1) pair_flags[threads + t / 64] = 0;
+                continue;
+            }
+            // the bit's edge to the last position; the row's other edges close up in front of it
+            int k = 0;
+            while (k < d && cols[k] != (uint16_t)v) ++k;
+            if (k == d) return "paired row does not hold its bit";
+            for (; k + 1 < d; ++k) {
+                cols[k] = cols[k + 1];
+                pos[k] = pos[k + 1];
+            }
+            const uint16_t dummy = (uint16_t)(s.e_pad + (slot & 63));
+            for (k = d - 1; k < last; ++k) {
+                cols[k] = (uint16_t)g.N;
+                pos[k] = dummy;
+            }
+            cols[last] = (uint16_t)v;
+            pos[last] = dummy;
+        }
+        if (v >= 0) pair_flags[t] = (uint8_t)(1 | (pr.first_r[t] ? 2 : 0));
+        if (v >= 0 && t >= half && pr.first_r[t]) return "first row at r = 1 on a thread of the capped half";
+    }
     return "";
 }
 

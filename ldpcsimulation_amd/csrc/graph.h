@@ -106,8 +106,11 @@ std::string load_alist(const char *path, ldpc_graph &g);
 // row_of_slot (optional, [threads * rpt], -1 = padding): the check row each row
 // slot holds; by default slot j holds row j. Any assignment gives the same
 // values (flooding rows are independent); it only moves work between waves.
+// skip_bit (optional, [N]): 1 = the bit gets no bit slot and its edges no c2v element
+// (they keep the padding position; build_pp_inreg_schedule).
 std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc, int rpt, RowSchedule &s,
-                               const std::vector<int> *row_of_slot = nullptr);
+                               const std::vector<int> *row_of_slot = nullptr,
+                               const std::vector<uint8_t> *skip_bit = nullptr);
 // Degree-aware row slots of the ping-pong kernel (rows_pp.hip; 512 check threads,
 // 2 rows each, dc 8): every row-0 slot and the row-1 slots of threads 256..511
 // -- the younger check wave of each SIMD runs only those -- hold rows of degree
@@ -117,4 +120,35 @@ std::string build_row_schedule(const ldpc_graph &g, int threads, int cpt, int dc
 // neighbours stay lane neighbours: coalesced gathers and scatters). Empty when
 // the rows do not fit that split.
 std::vector<int> pp_row_slots(const ldpc_graph &g, int threads, int dc_low);
+
+// In-register bits of the ping-pong kernel (rows_pp.hip k_rows_ppi). A degree-2 bit
+// whose two check rows are the two rows of one check thread never has to pass through
+// LDS: that thread holds both c2v messages (its prev registers) and is the only reader
+// of both v2c messages. pp_pair_rows matches rows over the degree-2 bits (a greedy walk
+// along the paths these bits span, exact for paths: the dual-diagonal parity part of the
+// 802.11n / 802.16e codes) and places every matched pair on one check thread, under
+// pp_row_slots' degree split (threads >= threads/2 hold degree <= dc_low in both rows,
+// the others degree <= dc_low in row 0); rows without a partner fill the remaining
+// slots as pp_row_slots does.
+struct PPPairing {
+    int pairs = 0;
+    std::vector<int> row_of_slot;     // [2 * threads] as pp_row_slots (-1 = empty)
+    std::vector<int> bit_of_thread;   // [threads] the thread's in-register bit, -1 = none
+    // [threads] 1: the thread's row 1 comes first in the bit's nlist (the sum order
+    // (yq + first) + second of decodeMinSum.cpp:452-476); threads >= threads/2 always 0
+    std::vector<uint8_t> first_r;
+};
+// false (out untouched beyond clearing): no pair, or the rows do not fit the split.
+bool pp_pair_rows(const ldpc_graph &g, int threads, int dc_low, int dc, PPPairing &out);
+// The row schedule over a pairing: build_row_schedule on its row slots with the
+// in-register bits left out of the bit-slot layout. In both rows of a paired thread the
+// bit's edge sits at the last position of the row's check node (dc_low - 1, or dc - 1 in
+// row 1 of threads < threads/2), gathers the bit's own app word (the staged channel
+// sample, which nobody overwrites: the bit has no bit slot) and scatters to the lane's
+// dummy slot. s.e_pad is the padded edge count of the smaller layout.
+// pair_flags [threads + threads/64]: per thread, bit 0 = paired, bit 1 = first_r; then per
+// wave 1 when every lane's last positions are in-register or padding edges (no lane of
+// the wave needs LDS for them), else 0.
+std::string build_pp_inreg_schedule(const ldpc_graph &g, int threads, int cpt, int dc, int dc_low,
+                                    const PPPairing &pr, RowSchedule &s, std::vector<uint8_t> &pair_flags);
 }  // namespace ldpc

@@ -52,6 +52,11 @@ struct RowSched {
     const uint8_t *cn_deg;          // [threads * rpt]
     const uint16_t *vn_col;         // [threads * cpt]
     const uint32_t *vn_info;        // [threads * cpt]
+    // the in-register schedule only (graph.h build_pp_inreg_schedule; null / 0 elsewhere)
+    const uint8_t *pair;            // [threads + threads / 64] per thread: bit 0 paired, bit 1 row 1 first; per wave: 1 = no LDS at the last positions
+    int e_used;                     // padded bit-slot edges of its layout (e_pad is the split schedule's: same LDS partition)
+    int n_inreg;                    // in-register bits
+    int lds_edge_slots;             // check-edge slots that pass through LDS per codeword-iteration
 };
 
 // Device copy of graph.h's FloodSchedule (global-memory flooding kernel).
@@ -103,7 +108,8 @@ struct LaunchPlan {
     int grid = 0;                   // blocks of the launch; flood_phase: resident slots K
     size_t scratch_per_block = 0;   // global scratch slot of one block / resident codeword
     size_t scratch_bytes = 0;       // scratch the launch needs in all
-    const RowSched *rs = nullptr;   // the row schedule the kernel reads (the context's rs or rs_pp)
+    const RowSched *rs = nullptr;   // the row schedule the plan describes (the context's rs or rs_pp)
+    const RowSched *rs_inreg = nullptr;   // rows_pp: the in-register schedule the kernel reads instead (k_rows_ppi)
     bool redo = false;              // fast row kernels: a redo list goes in and launch_redo follows
 };
 
@@ -118,6 +124,7 @@ struct PlanInput {
     const DecodeArgs &a;            // after nms_setup; a.batch sizes the grid
     bool f64;
     int maxdv = 0;                  // the code's largest column degree (plan_ddbmp)
+    const RowSched *rs_ppi = nullptr;   // the ping-pong kernel's in-register schedule (null: the code has no row pair)
 };
 
 // The (precision, sample source) template axes every kernel has: fn(type_tag<F>{}, src_tag<SRC>{}).
@@ -203,7 +210,16 @@ hipError_t launch_redo(const DevGraph &g, const DecodeArgs &a, bool f64, const u
 // overlapped (schedule: 512 threads, 2 rows and 4 bit slots each, dc 8, the
 // degree-aware row slots when rs.dc_low == 7); redo as above (fp32: MS and NMS
 // with the verified reciprocal, rows_fast_f32_ok). plan_rows_pp: as plan_rows_fast.
+// With PlanInput.rs_ppi (fp64, LDPC_OPT_PP_SLOTS 0) the launch is k_rows_ppi: the degree-2
+// bits that join a check thread's two rows stay in that thread's registers (graph.h
+// pp_pair_rows); the plan still describes the split schedule it is derived from.
 bool plan_rows_pp(const PlanInput &in, LaunchPlan &p);
+// Bit slots per thread of the in-register schedule: 3 where the bits left fit 3 x 512 slots
+// in at most 24 groups (the bench code: 1458 bits, 23 groups), else 4 as in the schedule it
+// derives from. LDPC_PP_INREG_CPT = 4 (A/B builds): always 4.
+#ifndef LDPC_PP_INREG_CPT
+#define LDPC_PP_INREG_CPT 3
+#endif
 hipError_t launch_rows_pp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *redo, hipStream_t s);
 
 // Row-kernel template bounds (host picks the smallest that fits).

@@ -35,6 +35,16 @@
 // (k_redo) after the launch; the other slot is unaffected. Rows past M (degree 0) gather app[N + 2] = +0, so
 // their messages stay 0 (their scatters land in per-lane dummy slots that the
 // padding edges of real rows also use; those read +inf - finite = +inf).
+//
+// k_rows_ppi (in-register bits, fp64 slots): a degree-2 bit whose two check rows are the two rows of
+// one check thread (graph.h pp_pair_rows: the dual-diagonal parity bits of the 802.11n
+// codes, one per check thread) has no bit slot and no c2v element. Its posterior
+// (yq + c2v_first) + c2v_second -- the bit node's sum in nlist order -- is formed by that
+// thread from its own prev registers and the staged yq (app[bit], which nobody overwrites)
+// at the start of the row's interval, and takes the place of the gather at the last
+// position of both rows' check nodes; the two scatters, the bit role's two reads and its
+// app write are not issued. The thread also forms the bit's decision, error weight and
+// share of both rows' syndrome from the final prev. Same values, same order of additions.
 #include "kernels.h"
 #include "device_common.h"
 #include "minsum_common.h"
@@ -134,6 +144,13 @@ namespace {
 // arithmetic (sched_group_barrier); 0: left to the scheduler.
 #ifndef LDPC_PP_GATHER_FIRST
 #define LDPC_PP_GATHER_FIRST 0
+#endif
+// k_rows_ppi, where the staged sample of a check thread's in-register bit lives: 0 one
+// ds_read_b64 of app[bit] per interval (nobody overwrites that word); 1 two registers per
+// slot, read back after B1 as the bit waves read their yq (pp_role IR == 1 only). Measured
+// 11.42-11.44 (1) against 11.52-11.54 ms (0) per bench launch.
+#ifndef LDPC_PP_INREG_Y
+#define LDPC_PP_INREG_Y 1
 #endif
 
 // Diagnostic builds (-DLDPC_STAMPS, `make ppvariant`): per wave, s_memtime cycles
@@ -388,11 +405,13 @@ __device__ __forceinline__ int wave_sum3(int x)
 // slot whose premise failed go to the re-decode list instead. Per lane the counts are
 // small -- a bit-role lane holds CPT = 4 bit slots and one Philox group of each
 // codeword (N <= 2048, rows_pp_supported), so its bit and uncoded errors are <= 4; a
-// check-role lane holds the 0/1 syndrome of its rows -- so each wave sums them by
+// check-role lane holds the 0/1 syndrome of its rows (and, k_rows_ppi, the error of its one
+// in-register bit) -- so each wave sums them by
 // ballots (wave_sum3; the syndrome is an OR) and lane 0 adds the wave's totals into
 // red[kPPRedSums ...] with LDS atomics: one barrier, and only thread 0 reads the totals
 // (it clears them for the next step).
-template <int C, bool HB>
+// WCHK: the check role's lanes carry bit errors too (the in-register bits, <= 1 per lane and codeword).
+template <int C, bool HB, bool WCHK = false>
 __device__ __forceinline__ void pp_account(const DecodeArgs &a, int *red, int grp, int (&sums)[6 * C], unsigned *redo,
                                            unsigned long long *acc)
 {
@@ -407,6 +426,10 @@ __device__ __forceinline__ void pp_account(const DecodeArgs &a, int *red, int gr
                 if (lane0 && u) atomicAdd(&tot[3 * q + 1], u);
             } else {
                 if (__builtin_amdgcn_ballot_w64(sums[3 * q + 2] != 0) && lane0) atomicAdd(&tot[3 * q + 2], 1);
+                if constexpr (WCHK) {
+                    const int w = wave_sum3(sums[3 * q]);
+                    if (lane0 && w) atomicAdd(&tot[3 * q], w);
+                }
                 if constexpr (LDPC_PP_CHAN_ALL || LDPC_PP_CHAN_SPLIT) {   // the check waves' share of the channel
                     const int u = wave_sum3(sums[3 * q + 1]);
                     if (lane0 && u) atomicAdd(&tot[3 * q + 1], u);
@@ -473,7 +496,13 @@ __device__ __forceinline__ bool pp_check_node(const Pack<F, C> (&xin)[DCA], Pack
 // one the degree-8 rows and the padding in its row 1 (DC1 = 8). A row of lower
 // degree than its DC has padding edges: +inf gathers (no effect on min, sign or
 // argmin) and scatters to the lane's dummy slot.
-template <typename F, int SRC, int DC0, int DC1, int CPT, int VAR, bool FDIV, int R, bool HB>
+// IR (k_rows_ppi, the in-register schedule of graph.h build_pp_inreg_schedule): 0 the
+// bit role, or every edge through LDS; 1 a check wave whose last positions (DC0 - 1 of row
+// 0, DC1 - 1 of row 1) are in-register or padding edges in every lane: one gather of the
+// staged yq (padding: +inf) and no scatter for them; 2 a check wave where some lanes hold
+// real edges there: both gathers and scatters are issued (the paired lanes' scatters go to
+// the dummy slot) and the in-register sum is selected per lane (rs.pair bit 0).
+template <typename F, int SRC, int DC0, int DC1, int CPT, int VAR, bool FDIV, int R, bool HB, int IR = 0>
 __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, const RowSched &rs,
                                         const PPSlots<Pack<F, PPCw<F>::C>> &s, unsigned *redo,
                                         unsigned long long *acc)
@@ -483,6 +512,10 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
     constexpr int DCX = 8;                    // schedule stride (rs.dc)
     constexpr int RR = R > 0 ? R : 1;   // array extents
     static_assert(DC0 <= DCX && DC1 <= DCX && (R == 0) == HB, "pp_role shape");
+    // IR needs LDPC_PP_NOB2 (yq staged canonical by the channel) and LDPC_PP_PREFETCH (both rows'
+    // gathers ahead of row 0); plan_rows_pp picks k_rows_ppi only in builds that have both
+    static_assert(IR == 0 || R == 2, "in-register bits: two rows per check thread");
+    constexpr int L0 = DC0 - 1, L1 = DC1 - 1;   // IR: the in-register edge's position in row 0 / row 1
     constexpr bool F64 = sizeof(F) == 8;
     const F kMax = F64 ? (F)kFast64Max : (F)1e30f;   // premise bound on |yq|
     const int tid = threadIdx.x, N = g.N, lane = tid & 63;
@@ -506,6 +539,30 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                 for (int q = 0; q < DCX / 2; ++q) colw[r][q] = (uint32_t)(N + 2) * 0x10001u;
         }
     }
+    // IR: the lane has an in-register bit (IR == 1: or a padding edge, which behaves as one whose
+    // sample is +inf); fr1: its row 1 comes first in the bit's nlist (never where DC0 == DC1)
+    [[maybe_unused]] bool has = IR == 1, fr1 = false;
+    if constexpr (IR != 0) {
+        const uint32_t pf = rs.pair[LDPC_CHK(tid, kPPRole, CHK_PP_GATHER)];
+        if (IR == 2) has = (pf & 1u) != 0;
+        fr1 = DC0 != DC1 && (pf & 2u) != 0;
+        // IR == 1: an empty row 0 keeps +0 edges, but the shared sample it gathers is a padding edge's +inf
+        if (IR == 1 && deg[0] == 0)
+            colw[0][L0 / 2] = (L0 & 1) ? (colw[0][L0 / 2] & 0xffffu) | ((uint32_t)N << 16)
+                                       : (colw[0][L0 / 2] & 0xffff0000u) | (uint32_t)N;
+    }
+    // IR: (yq + c2v_first) + c2v_second of slot X's in-register bit, from the staged yq `y`
+    // and the messages the two rows sent last (prev): the bit node's sum (:452-476)
+    [[maybe_unused]] auto inreg_sum = [&](auto Xc, const P &y) -> P {
+        constexpr int X = decltype(Xc)::value;
+        P sum;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const F p0 = prev[X][0][L0].v[c], p1 = prev[X][RR - 1][L1].v[c];
+            sum.v[c] = (y.v[c] + (fr1 ? p1 : p0)) + (fr1 ? p0 : p1);
+        }
+        return sum;
+    };
     // bit slots of schedule thread bt
     const int bt = tid - kPPRole;
     [[maybe_unused]] int vgb[CPT], vgd[CPT];
@@ -556,10 +613,10 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         [[maybe_unused]] int synd0[C];      // LDPC_PP_TAILFUSE: slot 0's syndrome (check role)
 #pragma unroll
         for (int q = 0; q < 2 * C; ++q) unc[q] = wdec[q] = 0;
-        if constexpr (LDPC_PP_CHAN_ALL && !HB) {   // the check waves take Philox groups too
-            if (!(LDPC_PP_TAILEXP & 1)) pp_channel<F, SRC>(a, s, N, grp, unc, tid, 2 * kPPRole);
-        }
         [[maybe_unused]] unsigned chan_bad = 0;   // LDPC_PP_NOB2: slots with an input past the premise
+        if constexpr (LDPC_PP_CHAN_ALL && !HB) {   // the check waves take Philox groups too
+            if (!(LDPC_PP_TAILEXP & 1)) pp_channel<F, SRC>(a, s, N, grp, unc, tid, 2 * kPPRole, &chan_bad);
+        }
         [[maybe_unused]] const bool split = LDPC_PP_CHAN_SPLIT && SRC == SRC_PHILOX && LDPC_PP_NOB2 &&
                                             !(LDPC_PP_TAILEXP & 1) && pp_plain_step(a, N, grp, C);
         if constexpr (LDPC_PP_CHAN_SPLIT && !HB) {   // the check waves' share of a plain step
@@ -589,7 +646,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 #pragma unroll
                         for (int c = 0; c < C; ++c) prev[X][r][k].v[c] = F(0);
         }
-        if constexpr (LDPC_PP_CHAN_SPLIT && !HB) {   // the check waves' share of the channel's flags
+        if constexpr ((LDPC_PP_CHAN_SPLIT || (LDPC_PP_CHAN_ALL && LDPC_PP_NOB2)) && !HB) {   // the check waves' share of the channel's flags
             if (__builtin_amdgcn_ballot_w64(chan_bad != 0)) {
                 if (chan_bad & 1u) s.red[0] = 1;
                 if (chan_bad & 2u) s.red[1] = 1;
@@ -677,6 +734,18 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                 w[q] = e;
             }
         };
+        constexpr bool YREG = IR == 1 && LDPC_PP_INREG_Y;
+        [[maybe_unused]] P yreg[2];   // LDPC_PP_INREG_Y: the in-register bit's staged sample per slot
+        if constexpr (YREG) {
+#pragma unroll
+            for (int X = 0; X < 2; ++X) yreg[X] = s.app[X][LDPC_CHK(u16_at<DCX>(colw[0], L0), N + 3, CHK_PP_GATHER)];
+        }
+        // IR: the in-register bit's final posterior per slot (inreg_final, once the slot's last check phase is done)
+        [[maybe_unused]] P ipost[2];
+        [[maybe_unused]] auto inreg_final = [&](auto Xc) {
+            constexpr int X = decltype(Xc)::value;
+            ipost[X] = inreg_sum(Xc, YREG ? yreg[X] : s.app[X][LDPC_CHK(u16_at<DCX>(colw[0], L0), N + 3, CHK_PP_GATHER)]);
+        };
         // Syndrome of slot X's codeword c (rows; padding edges read +inf: parity 0; rows past M skipped)
         auto syndrome = [&](int X, int c) -> int {
             int synd = 0;
@@ -685,8 +754,12 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                     constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
                     int par = 0;
 #pragma unroll
-                    for (int k = 0; k < DCr; ++k)
-                        par ^= (s.app[X][LDPC_CHK(u16_at<DCX>(colw[r], k), N + 3, CHK_PP_GATHER)].v[c] > F(0)) ? 0 : 1;
+                    for (int k = 0; k < DCr; ++k) {
+                        if (IR == 1 && k == DCr - 1) continue;   // the in-register edge: below
+                        const int neg = (s.app[X][LDPC_CHK(u16_at<DCX>(colw[r], k), N + 3, CHK_PP_GATHER)].v[c] > F(0)) ? 0 : 1;
+                        par ^= (IR == 2 && k == DCr - 1 && has) ? 0 : neg;
+                    }
+                    if constexpr (IR != 0) par ^= (has && !(ipost[X].v[c] > F(0))) ? 1 : 0;
                     synd |= deg[r] > 0 ? par : 0;
                 });
             }
@@ -708,7 +781,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                     static_for<0, (LDPC_PP_PREFETCH ? R : 1)>([&](auto rc) {
                         constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
 #pragma unroll
-                        for (int k = 0; k < DCr; ++k)
+                        for (int k = 0; k < DCr - (IR == 1 && (r == 1 || YREG) ? 1 : 0); ++k)   // IR == 1: row 1's last edge is row 0's
                             xin[r][k] = lds_at<P>((LDPC_PP_EXP == 5 || LDPC_PP_EXP == 7) ? ab + 8u * (uint32_t)(lane + 64 * (k + 8 * r))
                                                                                          : LDPC_ADDR8(DCX, colw[r], k, ab, N + 3, CHK_PP_GATHER));
                     });
@@ -739,6 +812,15 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             if constexpr (R > 0) {
                 if (rows && LDPC_PP_EXP != 2) {
                     const uint32_t ab = s.app_base[X], cb = s.c2v_base[X];
+                    if constexpr (IR != 0) {   // the in-register bit's posterior in place of both rows' last gather
+                        if constexpr (YREG) xin[0][L0] = yreg[X];
+                        const P sum = inreg_sum(Xc, xin[0][L0]);
+#pragma unroll
+                        for (int c = 0; c < C; ++c) {
+                            xin[0][L0].v[c] = has ? sum.v[c] : xin[0][L0].v[c];
+                            xin[RR - 1][L1].v[c] = has ? sum.v[c] : xin[RR - 1][L1].v[c];
+                        }
+                    }
                     static_for<0, R>([&](auto rc) {
                         constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
                         if (!LDPC_PP_PREFETCH && r > 0) {
@@ -748,6 +830,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                         bool ok = true;
                         // the scatter of edge k into the bit-slot layout (experiments: none, or lane-contiguous)
                         auto store = [&](int k, const P &m) {
+                            if (IR == 1 && k == DCr - 1) return;   // in-register (k is a constant once inlined)
                             if constexpr (LDPC_PP_EXP != 4)
                                 lds_put<P>((LDPC_PP_EXP == 6 || LDPC_PP_EXP == 7)
                                                ? cb + 8u * (uint32_t)(lane + 64 * ((k + 8 * r + 16 * (tid >> 6)) % 112))
@@ -788,6 +871,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         if (a.T > 0) {
             interval(std::integral_constant<int, 0>(), false, true, true);
             if (TF && !(LDPC_PP_TAILEXP & 2)) {   // slot 0's posteriors are final
+                if constexpr (IR != 0) inreg_final(std::integral_constant<int, 0>());
 #pragma unroll
                 for (int c = 0; c < C; ++c) synd0[c] = syndrome(0, c);
             }
@@ -800,7 +884,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 
         if (LDPC_PP_TAILEXP & 2) {   // timing only: no syndrome, decisions or error weights
             int sums[6 * C] = {};
-            pp_account<C, HB>(a, s.red, grp, sums, redo, acc);
+            pp_account<C, HB, IR != 0>(a, s.red, grp, sums, redo, acc);
             continue;
         }
         // syndrome and decisions / error weight of the step's codewords (what the last
@@ -817,6 +901,26 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                 }
             }
         }
+        if constexpr (IR != 0) {
+            // the in-register bit: posterior, decision and error weight by its check thread (:270, :382-393)
+            inreg_final(std::integral_constant<int, 0>());
+            inreg_final(std::integral_constant<int, 1>());
+            const int v = u16_at<DCX>(colw[0], L0);
+            if (has && v < N) {   // IR == 1: a padding edge's index is N
+#pragma unroll
+                for (int q = 0; q < 2 * C; ++q) {
+                    const int b = grp * 2 * C + q;
+                    if (b >= a.batch) continue;
+                    const int8_t *cvec =
+                        SRC == SRC_GIVEN ? (a.c ? a.c + (size_t)b * N : nullptr)
+                                         : (a.cw_table ? a.cw_table + (size_t)((a.first_cw + (uint64_t)b) % (uint64_t)a.cw_rows) * N
+                                                       : nullptr);
+                    const int d = ipost[q / C].v[q % C] > F(0) ? 1 : -1;   // :471-474
+                    wdec[q] += d != (cvec ? cvec[v] : 1);
+                    if (a.d_out) a.d_out[(size_t)b * N + v] = (int8_t)d;
+                }
+            }
+        }
         int sums[6 * C];
 #pragma unroll
         for (int X = 0; X < 2; ++X) {
@@ -829,7 +933,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             }
         }
         PP_STAMP_ACC(5);
-        pp_account<C, HB>(a, s.red, grp, sums, redo, acc);
+        pp_account<C, HB, IR != 0>(a, s.red, grp, sums, redo, acc);
     }
     PP_STAMP_OUT()
 }
@@ -847,9 +951,12 @@ LDPC_CHECK_TU(rows_pp)
 // SPLIT: the schedule has degree-aware row slots (rs.dc_low == 7, graph.h
 // pp_row_slots): check waves 4-7 run two 7-edge rows, waves 0-3 a 7-edge and an
 // 8-edge row. Otherwise every row runs the 8-edge check node.
-template <typename F, int SRC, int CPT, int VAR, bool FDIV, bool SPLIT>
-__global__ __launch_bounds__(2 * kPPRole) void k_rows_pp(DecodeArgs a, DevGraph g, RowSched rs, unsigned *redo)
+// INREG (k_rows_ppi; SPLIT): rs is the in-register schedule, and each check wave runs the role
+// rs.pair names for it (pp_role IR 1 or 2).
+template <typename F, int SRC, int CPT, int VAR, bool FDIV, bool SPLIT, bool INREG>
+__device__ __forceinline__ void pp_kernel(const DecodeArgs &a, const DevGraph &g, const RowSched &rs, unsigned *redo)
 {
+    static_assert(!INREG || SPLIT, "in-register bits come with the degree-aware row slots");
     using P = Pack<F, PPCw<F>::C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #pragma unroll
@@ -874,7 +981,18 @@ __global__ __launch_bounds__(2 * kPPRole) void k_rows_pp(DecodeArgs a, DevGraph 
         if (wave >= kPPRole / 128) __builtin_amdgcn_s_setprio(2);
         else __builtin_amdgcn_s_setprio(1);
     }
-    if (!low)
+    if constexpr (INREG) {
+        const bool pure = low && __builtin_amdgcn_readfirstlane((int)rs.pair[kPPRole + (low ? wave : 0)]) != 0;
+        if (!low)
+            pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 0, true>(a, g, rs, s, redo, acc);
+        else if (wave >= kPPRole / 128) {
+            if (pure) pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 1>(a, g, rs, s, redo, acc);
+            else pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 2>(a, g, rs, s, redo, acc);
+        } else {
+            if (pure) pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 1>(a, g, rs, s, redo, acc);
+            else pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 2>(a, g, rs, s, redo, acc);
+        }
+    } else if (!low)
         pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 0, true>(a, g, rs, s, redo, acc);
     else if (!SPLIT)
         pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 2, false>(a, g, rs, s, redo, acc);
@@ -889,6 +1007,20 @@ __global__ __launch_bounds__(2 * kPPRole) void k_rows_pp(DecodeArgs a, DevGraph 
     }
 }
 
+template <typename F, int SRC, int CPT, int VAR, bool FDIV, bool SPLIT>
+__global__ __launch_bounds__(2 * kPPRole) void k_rows_pp(DecodeArgs a, DevGraph g, RowSched rs, unsigned *redo)
+{
+    pp_kernel<F, SRC, CPT, VAR, FDIV, SPLIT, false>(a, g, rs, redo);
+}
+
+// The degree-aware slots with the paired rows' degree-2 bits in registers (the header, graph.h
+// pp_pair_rows): rs is the in-register schedule.
+template <typename F, int SRC, int CPT, int VAR, bool FDIV>
+__global__ __launch_bounds__(2 * kPPRole) void k_rows_ppi(DecodeArgs a, DevGraph g, RowSched rs, unsigned *redo)
+{
+    pp_kernel<F, SRC, CPT, VAR, FDIV, true, true>(a, g, rs, redo);
+}
+
 static int rows_pp_lds_bytes(const DevGraph &g, const RowSched &rs)
 {
     return (int)(2 * (size_t)pp_slot_words(g.N, rs.e_pad + 64) * 8 + kPPRedInts * sizeof(int));
@@ -898,13 +1030,16 @@ static bool rows_pp_supported(const DevGraph &g, const RowSched &rs)
 {
     // N <= 4 * kPPRole: a bit-role lane then holds <= 4 bits and one Philox group per
     // codeword, the bound pp_account's ballot-sliced wave sums rely on
-    return rs.threads == kPPRole && rs.rpt == 2 && rs.cpt == 4 && rs.dc == 8 && (rs.dc_low == 0 || rs.dc_low == 7) &&
+    return rs.threads == kPPRole && rs.rpt == 2 && (rs.cpt == 4 || (rs.pair && rs.cpt == 3)) && rs.dc == 8 && (rs.dc_low == 0 || rs.dc_low == 7) &&
            g.N <= 4 * kPPRole && g.N + 3 <= 0xffff && rows_pp_lds_bytes(g, rs) <= 160 * 1024;
 }
 
 template <typename F, int SRC, int VAR, bool FDIV>
 static const void *pp_fn_t(const RowSched &rs)
 {
+    if constexpr (sizeof(F) == 8)   // fp32 pairs measured slower with in-register bits: fp64 only
+        if (rs.pair)
+            return rs.cpt == 3 ? (const void *)k_rows_ppi<F, SRC, 3, VAR, FDIV> : (const void *)k_rows_ppi<F, SRC, 4, VAR, FDIV>;
     return rs.dc_low == 7 ? (const void *)k_rows_pp<F, SRC, 4, VAR, FDIV, true>
                           : (const void *)k_rows_pp<F, SRC, 4, VAR, FDIV, false>;
 }
@@ -931,13 +1066,21 @@ bool plan_rows_pp(const PlanInput &in, LaunchPlan &p)
     // The ping-pong kernel's schedule: the degree-aware row slots (graph.h
     // pp_row_slots) when the code admits them, else the row kernel's
     // (LDPC_OPT_PP_SLOTS = 1, tests / A/B: always the row kernel's slots).
+    // fp64, LDPC_OPT_PP_SLOTS = 0 on a code with row pairs: k_rows_ppi on the in-register schedule
+    // derived from the degree-aware one (the same LDS partition; the plan reports the latter);
+    // 2: every bit in LDS on the degree-aware slots.
     const RowSched *rs = in.rs_pp && opt(LDPC_OPT_PP_SLOTS) != 1 ? in.rs_pp : in.rs;
     if (!rows_pp_supported(in.g, *rs)) return false;
+    const RowSched *ri = nullptr;
+    if (in.f64 && LDPC_PP_NOB2 && LDPC_PP_PREFETCH && rs == in.rs_pp && in.rs_ppi && opt(LDPC_OPT_PP_SLOTS) == 0 &&
+        rs->dc_low == 7 && in.rs_ppi->pair && in.rs_ppi->e_pad == rs->e_pad && rows_pp_supported(in.g, *in.rs_ppi))
+        ri = in.rs_ppi;
     p.kernel = Kernel::rows_pp;
     p.name = "rows_pp";
     p.redo = true;
     p.rs = rs;
-    p.fn = pp_fn(*rs, in.a, in.f64);
+    p.rs_inreg = ri;
+    p.fn = pp_fn(ri ? *ri : *rs, in.a, in.f64);
     p.threads = 2 * kPPRole;
     p.lds_bytes = rows_pp_lds_bytes(in.g, *rs);
     p.blocks_per_cu = 1;   // one 1024-thread block per CU
@@ -948,7 +1091,7 @@ bool plan_rows_pp(const PlanInput &in, LaunchPlan &p)
 
 hipError_t launch_rows_pp(const LaunchPlan &p, const DevGraph &g, const DecodeArgs &a, unsigned *redo, hipStream_t s)
 {
-    void *args[] = {(void *)&a, (void *)&g, (void *)p.rs, &redo};
+    void *args[] = {(void *)&a, (void *)&g, (void *)(p.rs_inreg ? p.rs_inreg : p.rs), &redo};
     return launch_fn(p, args, s);
 }
 

@@ -31,7 +31,7 @@ OPTIONS = {"rows64": 1, "rows32": 2, "pp_slots": 3, "kernel": 4, "flood_mode": 5
 EMS_OPTIONS = ("ems_threads", "ems_swizzle")
 # symbolic values of the kernel-choice options
 OPTION_VALUES = {"rows64": {"pp": 0, "fast": 1, "rows": 2}, "rows32": {"pp": 0, "fast": 1, "rows": 2},
-                 "pp_slots": {"split": 0, "plain": 1}, "kernel": {"auto": 0, "lds": 1, "flood": 2, "global": 3},
+                 "pp_slots": {"split": 0, "plain": 1, "split_lds": 2}, "kernel": {"auto": 0, "lds": 1, "flood": 2, "global": 3},
                  "flood_mode": {"phase": 0, "persistent": 1}, "flood_msg": {"packed": 0, "c2v": 1},
                  "bp_kernel": {"rows": 0, "generic": 1}, "gdbf_kernel": {"rows": 0, "generic": 1},
                  "ddbmp_kernel": {"rows": 0, "generic": 1},
@@ -326,6 +326,7 @@ _SIG = {
     "ldpc_ctx_kernel_info": (_info(_Cfg) + [_pi32], _i32),
     "ldpc_ctx_redo_count": ([_vp, C.POINTER(C.c_int64)], _i32),
     "ldpc_ctx_row_sched_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
+    "ldpc_ctx_pp_inreg_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
     "ldpc_ctx_set_option": ([_vp, _i32, _i32], _i32),
     "ldpc_ctx_get_option": ([_vp, _i32, _pi32], _i32),
     "ldpc_nb_ctx_set_option": ([_vp, _i32, _i32], _i32),
@@ -370,6 +371,10 @@ EXPORTED = list(_SIG)
 _lib = None
 
 
+# exports added without an ABI bump: the product library has them, an older A/B build may not
+_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info"}
+
+
 def lib():
     global _lib
     if _lib is not None:
@@ -386,6 +391,8 @@ def lib():
         pass
     L = C.CDLL(LIB_PATH)
     for name, (argt, rest) in _SIG.items():
+        if name in _ADDED_IN_ABI and not hasattr(L, name):
+            continue   # an A/B library (use_library, bench.py --lib) of this ABI built before the export
         fn = getattr(L, name)
         fn.argtypes = argt
         fn.restype = rest
@@ -626,6 +633,13 @@ class Context:
         _check(lib().ldpc_ctx_row_sched_info(self._h, C.byref(cfg._c()), info.ctypes.data))
         keys = ("threads", "rows_per_thread", "slots_per_thread", "dc", "e_pad", "cw_per_block", "lds_bytes",
                 "blocks_per_cu", "dc_low", "issued_check_edges")
+        return {k: int(v) for k, v in zip(keys, info)}
+
+    def pp_inreg_info(self, cfg: DecoderConfig) -> dict:
+        """The ping-pong kernel's in-register bits for cfg (raises LdpcError UNSUPPORTED for other kernels)."""
+        info = np.zeros(4, dtype=np.int32)
+        _check(lib().ldpc_ctx_pp_inreg_info(self._h, C.byref(cfg._c()), info.ctypes.data))
+        keys = ("inreg_bits", "lds_check_edges", "bit_slot_edges", "slots_per_thread")
         return {k: int(v) for k, v in zip(keys, info)}
 
     def kernel_info(self, cfg: DecoderConfig) -> dict:
