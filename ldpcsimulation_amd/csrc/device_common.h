@@ -47,8 +47,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
 // correctly-rounded logf / sqrtf / sincospif took ~100 with their range and denormal
 // branches. r >= 2^-33 is a normal float, so the hardware log is within an ulp or two; the
 // normals differ from the OCML transform's in the last bits only, which no Gaussian
-// statistic resolves (test_channel_noise_statistics, the FER z-tests). LDPC_BM_OCML=1
-// (variant builds) keeps the OCML transform for A/B.
+// statistic resolves (test_channel_noise_statistics, the FER z-tests). Measured against the
+// float64 transform of the same uniforms, sample by sample: at most 2.5 x 2^-23 max(1, |n|)
+// (tests/test_philox_channel.py). LDPC_BM_OCML=1 (variant builds) keeps the
+// OCML transform for A/B.
 #ifndef LDPC_BM_OCML
 #define LDPC_BM_OCML 0
 #endif

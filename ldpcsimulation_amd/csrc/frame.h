@@ -20,7 +20,9 @@ __device__ __forceinline__ const int8_t *frame_codeword(const Args &a, int b, in
 
 // The channel samples of bits 4 * g4 .. 4 * g4 + 3 of frame b. SRC_GIVEN: from a.y, 1 past N.
 // SRC_PHILOX: y = c (1 + sigma n), n from Philox4x32-10 keyed by the seed at counter
-// (g4, codeword number, stream_id) + Box-Muller; written to y_out (may be null) up to N.
+// (g4, lo32(cw), hi32(cw), stream_id) + Box-Muller; written to y_out (may be null) up to N.
+// DESIGN §5a has the layout of every stream (it is a contract: checkpoints and sharded
+// sweeps rely on it) and tests/test_philox_channel.py compares every sample with it.
 // Like MAD64, Y_AFTER is each site's choice and changes no value: the y_out store sits in the
 // sample loop, or in a loop after it (layered.hip; bp.hip, its fp64 rows kernel excepted). In
 // the sample loop k_bp_global<double, 16> takes 148 VGPRs instead of 127 and the fp64 layered
