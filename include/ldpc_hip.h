@@ -258,6 +258,9 @@ int  ldpc_ctx_kernel_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, char *name
  * the fast kernel). Diagnostic of the fast/exact split; synchronises the
  * stream. No reference counterpart (the reference has one exact path). */
 int  ldpc_ctx_redo_count(ldpc_ctx *ctx, int64_t *n);
+/* The batch indices of those codewords, in the order the kernel listed them (any order):
+ * *n = their number, the first min(*n, cap) of them to list[]. Synchronises the stream. */
+int  ldpc_ctx_redo_list(ldpc_ctx *ctx, uint32_t *list, int64_t cap, int64_t *n);
 /* Shape of the row kernel ("rows"/"rows_fast"/"rows_pp"/"rows_es") that decodes cfg, for the
  * on-chip (LDS) roofline model of bench.py: info[10] = {threads per block,
  * rows per thread, bit slots per thread, padded row degree, padded edge slots
@@ -276,6 +279,15 @@ int  ldpc_ctx_row_sched_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t
  * schedule. LDPC_ERR_UNSUPPORTED when the kernel that decodes cfg is not "rows_pp". Host-only.
  * No reference counterpart. */
 int  ldpc_ctx_pp_inreg_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t *info);
+/* The check-row slots of the schedule the "rows_pp" kernel runs cfg on, read back from the
+ * device (the in-register schedule where ldpc_ctx_pp_inreg_info reports bits, else
+ * ldpc_ctx_row_sched_info's): slot j belongs to check thread j % threads as its row
+ * j / threads; cols[8 * j + k] is the bit of its edge k (an entry >= N is a padding edge),
+ * deg[j] its degree (0: an empty slot). *nslots = threads * rows per thread; cap is the room
+ * of cols / 8 and deg. Diagnostic, for tests that aim at one row of a thread; synchronises
+ * the stream. LDPC_ERR_UNSUPPORTED as above. No reference counterpart. */
+int  ldpc_ctx_pp_row_slots(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, uint16_t *cols, uint8_t *deg, int cap,
+                           int *nslots);
 
 /* ---- kernel-selection options (ABI 10) ------------------------------- */
 /* The library picks the kernel for a cfg by itself (the reference fixes its

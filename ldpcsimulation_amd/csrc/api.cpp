@@ -878,6 +878,23 @@ int ldpc_ctx_pp_inreg_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *in
     return LDPC_OK;
 }
 
+int ldpc_ctx_pp_row_slots(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, uint16_t *cols, uint8_t *deg, int cap, int *nslots)
+{
+    if (!cols || !deg || !nslots || cap < 0) return set_err(LDPC_ERR_INVALID, "null argument");
+    ldpc::LaunchPlan p;
+    RC_TRY(info_plan(c, cfg, p));
+    if (p.kernel != ldpc::Kernel::rows_pp || !p.rs)
+        return set_err(LDPC_ERR_UNSUPPORTED, "the ping-pong kernel does not decode this cfg (kernel %s)", p.name);
+    const ldpc::RowSched *rs = p.rs_inreg ? p.rs_inreg : p.rs;   // the schedule launch_rows_pp passes to the kernel
+    *nslots = rs->threads * rs->rpt;
+    if (cap < *nslots) return set_err(LDPC_ERR_INVALID, "%d row slots, room for %d", *nslots, cap);
+    RC_TRY(c->enter());
+    HIP_TRY(hipMemcpyAsync(cols, rs->cn_cols, sizeof(uint16_t) * (size_t)*nslots * rs->dc, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(deg, rs->cn_deg, sizeof(uint8_t) * (size_t)*nslots, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return LDPC_OK;
+}
+
 int ldpc_ctx_redo_count(ldpc_ctx *c, int64_t *n)
 {
     if (!c || !n) return set_err(LDPC_ERR_INVALID, "null argument");
@@ -888,6 +905,19 @@ int ldpc_ctx_redo_count(ldpc_ctx *c, int64_t *n)
     HIP_TRY(hipMemcpyAsync(&h, c->redo.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *n = (int64_t)h;
+    return LDPC_OK;
+}
+
+int ldpc_ctx_redo_list(ldpc_ctx *c, uint32_t *list, int64_t cap, int64_t *n)
+{
+    if (!c || !n || cap < 0 || (cap > 0 && !list)) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(ldpc_ctx_redo_count(c, n));
+    const int64_t m = std::min(*n, cap);
+    if (m > 0) {
+        HIP_TRY(hipMemcpyAsync(list, (const unsigned *)c->redo.p + 1, sizeof(unsigned) * (size_t)m, hipMemcpyDeviceToHost,
+                               c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
     return LDPC_OK;
 }
 

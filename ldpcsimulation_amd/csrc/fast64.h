@@ -74,11 +74,6 @@ __device__ __forceinline__ double norm64(double m, double alpha, double rcp, dou
     }
 }
 
-// fp64 fast check node over edges [0, DC) of the arrays (extent DCA >= DC; the
-// entries past DC are not touched). xin: the app values gathered for the row's
-// edges (padding edges read +inf); pv: in = c2v sent last iteration, out = the
-// new c2v. Returns false when the premise may fail for the next iteration (or
-// failed for this one's division).
 // VALU instructions the scheduler places ahead of each edge's store (ORDER).
 #ifndef LDPC_FAST64_CMPFIRST
 #define LDPC_FAST64_CMPFIRST 0
@@ -86,24 +81,105 @@ __device__ __forceinline__ double norm64(double m, double alpha, double rcp, dou
 #ifndef LDPC_FAST64_STORE_VALU
 #define LDPC_FAST64_STORE_VALU 3
 #endif
+// cn_fast64's defaults: no sink, no filler
+struct NoSink {
+    __device__ __forceinline__ void operator()(int, const Pack<double, 1> &) const {}
+};
+struct NoFill {
+    __device__ __forceinline__ void operator()(int) const {}
+};
+// The front of a 7- or 8-edge check node -- the v2c subtractions, the two_min tournament and
+// the sign parity -- as a numbered list of single operations with two_min's tree and operand
+// order, so that a caller can issue a fixed number of them at places of its choice (the
+// ping-pong kernel puts row 1's front into row 0's store chain, rows_pp.hip LDPC_PP_ILV).
+// After steps 0 .. N-1, x, mn1, mn2 and par hold what cn_fast64's own front computes.
+template <int DC>
+struct CnFront64 {
+    static_assert(DC == 7 || DC == 8, "CnFront64: the ping-pong kernel's check-node degrees");
+    static constexpr int NSUB = DC, NTOUR = DC == 7 ? 17 : 20, NPAR = (DC + 1) / 2, N = NSUB + NTOUR + NPAR;
+    double x[DC], mn1, mn2;
+    double l1, l2, r1, r2, t[4];
+    uint32_t par;
+    __device__ __forceinline__ double ax(int k) const { return __builtin_fabs(x[k]); }
+    // step J of two_min<K0, 3> (5 steps) and two_min<K0, 4> (8 steps) into (m1, m2)
+    template <int J, int K0>
+    __device__ __forceinline__ void three(double &m1, double &m2)
+    {
+        if constexpr (J == 0) t[0] = __builtin_fmin(ax(K0), ax(K0 + 1));
+        else if constexpr (J == 1) t[1] = __builtin_fmax(ax(K0), ax(K0 + 1));
+        else if constexpr (J == 2) m1 = __builtin_fmin(t[0], ax(K0 + 2));
+        else if constexpr (J == 3) t[2] = __builtin_fmax(t[0], ax(K0 + 2));
+        else m2 = __builtin_fmin(t[1], t[2]);
+    }
+    template <int J, int K0>
+    __device__ __forceinline__ void four(double &m1, double &m2)
+    {
+        if constexpr (J == 0) t[0] = __builtin_fmin(ax(K0), ax(K0 + 1));
+        else if constexpr (J == 1) t[1] = __builtin_fmax(ax(K0), ax(K0 + 1));
+        else if constexpr (J == 2) t[2] = __builtin_fmin(ax(K0 + 2), ax(K0 + 3));
+        else if constexpr (J == 3) t[3] = __builtin_fmax(ax(K0 + 2), ax(K0 + 3));
+        else if constexpr (J == 4) m1 = __builtin_fmin(t[0], t[2]);
+        else if constexpr (J == 5) t[0] = __builtin_fmax(t[0], t[2]);
+        else if constexpr (J == 6) t[1] = __builtin_fmin(t[1], t[3]);
+        else m2 = __builtin_fmin(t[0], t[1]);
+    }
+    template <int I, int DCA>
+    __device__ __forceinline__ void step(const Pack<double, 1> (&xin)[DCA], const Pack<double, 1> (&pv)[DCA])
+    {
+        constexpr int NL = DC == 7 ? 5 : 8;   // steps of the left half's tournament
+        if constexpr (I < NSUB) {
+            x[I] = xin[I].v[0] - pv[I].v[0];   // v2c (:469)
+        } else if constexpr (I < NSUB + NTOUR) {
+            constexpr int J = I - NSUB;
+            if constexpr (J < NL) {
+                if constexpr (DC == 7) three<J, 0>(l1, l2);
+                else four<J, 0>(l1, l2);
+            } else if constexpr (J < NL + 8) {
+                four<J - NL, DC / 2>(r1, r2);
+            } else if constexpr (J == NL + 8) mn1 = __builtin_fmin(l1, r1);
+            else if constexpr (J == NL + 9) t[0] = __builtin_fmax(l1, r1);
+            else if constexpr (J == NL + 10) t[1] = __builtin_fmin(l2, r2);
+            else mn2 = __builtin_fmin(t[0], t[1]);
+        } else {
+            constexpr int Q = I - NSUB - NTOUR;
+            if constexpr (2 * Q + 1 < DC)
+                par = __builtin_amdgcn_bitop3_b32(Q == 0 ? 0u : par, hi32(x[2 * Q]), hi32(x[2 * Q + 1]), 0x96);
+            else
+                par ^= hi32(x[DC - 1]);
+        }
+    }
+};
+
+// cn_fast64 behind its front: normalisation, premise, and per edge the select, sign merge and
+// sink. fill(k) runs after edge k's sink; with ORDER its FILLN VALU operations join edge k's
+// pinned group, ahead of the edge's store.
+template <int DC, int VAR, bool FDIV, int DCA, typename Sink, bool ORDER, bool ACC, typename Fill = NoFill, int FILLN = 0>
+__device__ __forceinline__ bool cn_fast64_back(const double (&x)[DC], double mn1, double mn2, uint32_t par,
+                                               Pack<double, 1> (&pv)[DCA], double alpha, double rcp, double delta,
+                                               Sink sink, uint32_t *pacc, Fill fill = Fill());
+
+// fp64 fast check node over edges [0, DC) of the arrays (extent DCA >= DC; the
+// entries past DC are not touched). xin: the app values gathered for the row's
+// edges (padding edges read +inf); pv: in = c2v sent last iteration, out = the
+// new c2v. Returns false when the premise may fail for the next iteration (or
+// failed for this one's division).
 // ACC (the ping-pong kernel): instead of the f64 premise compare, the row folds
 // hi32(M2) into the maximum *pacc (one v_max_u32; M2 >= +0 or NaN, so M2 < 2^1000 <=>
 // hi32(M2) < kFast64MaxHi as u32, NaN and inf above it), and a tiny minimum forces
 // *pacc to ~0; the caller tests it (per row, or once per codeword when *pacc is a
 // sticky per-slot maximum: rows_pp.hip LDPC_PP_STICKY). Same set of re-decoded codewords.
-struct NoSink {
-    __device__ __forceinline__ void operator()(int, const Pack<double, 1> &) const {}
-};
 // sink(k, message) is called as each new message is formed (a store of it, say);
 // with ORDER the scheduler is asked to keep that per-edge order (the selects of
 // edge k, then its store), so the stores start while later edges are computed
 // instead of trailing the whole row.
-template <int DC, int VAR, bool FDIV, int DCA, typename Sink = NoSink, bool ORDER = false, bool ACC = false>
+// Fill, FILLN: cn_fast64_back's filler (off in k_rows_fast and wherever it is not named).
+template <int DC, int VAR, bool FDIV, int DCA, typename Sink = NoSink, bool ORDER = false, bool ACC = false,
+          typename Fill = NoFill, int FILLN = 0>
 __device__ __forceinline__ bool cn_fast64(const Pack<double, 1> (&xin)[DCA], Pack<double, 1> (&pv)[DCA], double alpha,
-                                          double rcp, double delta, Sink sink = Sink(), uint32_t *pacc = nullptr)
+                                          double rcp, double delta, Sink sink = Sink(), uint32_t *pacc = nullptr,
+                                          Fill fill = Fill())
 {
     static_assert(DC >= 1 && DC <= DCA, "cn_fast64 degree");
-    constexpr uint32_t SIGN = 0x80000000u;
     double x[DC];
 #pragma unroll
     for (int k = 0; k < DC; ++k) x[k] = xin[k].v[0] - pv[k].v[0];   // v2c (:469)
@@ -113,6 +189,16 @@ __device__ __forceinline__ bool cn_fast64(const Pack<double, 1> (&xin)[DCA], Pac
 #pragma unroll
     for (int k = 0; k + 1 < DC; k += 2) par = __builtin_amdgcn_bitop3_b32(par, hi32(x[k]), hi32(x[k + 1]), 0x96);
     if (DC & 1) par ^= hi32(x[DC - 1]);
+    return cn_fast64_back<DC, VAR, FDIV, DCA, Sink, ORDER, ACC, Fill, FILLN>(x, mn1, mn2, par, pv, alpha, rcp, delta, sink,
+                                                                              pacc, fill);
+}
+
+template <int DC, int VAR, bool FDIV, int DCA, typename Sink, bool ORDER, bool ACC, typename Fill, int FILLN>
+__device__ __forceinline__ bool cn_fast64_back(const double (&x)[DC], double mn1, double mn2, uint32_t par,
+                                               Pack<double, 1> (&pv)[DCA], double alpha, double rcp, double delta,
+                                               Sink sink, uint32_t *pacc, Fill fill)
+{
+    constexpr uint32_t SIGN = 0x80000000u;
     const double M1 = norm64<VAR, FDIV>(mn1, alpha, rcp, delta), M2 = norm64<VAR, FDIV>(mn2, alpha, rcp, delta);
     // M2 < 2^1000 (also false for NaN; M1 <= M2 covers the row). The u32 form compares the
     // high words (M2 >= +0; 2^1000's low word is 0).
@@ -169,8 +255,9 @@ __device__ __forceinline__ bool cn_fast64(const Pack<double, 1> (&xin)[DCA], Pac
         const uint32_t m = (VAR == V_OMS) ? (eq ? mk2 : mk1) : SIGN;
         pv[k].v[0] = mkd(l, __builtin_amdgcn_bitop3_b32(h, hi32(x[k]), m, 0x78));   // h ^ (v2c_k & m)
         sink(k, pv[k]);
+        fill(k);
         if constexpr (ORDER) {
-            __builtin_amdgcn_sched_group_barrier(0x2, LDPC_FAST64_STORE_VALU, 0);   // VALU: compare, selects, sign merge, address
+            __builtin_amdgcn_sched_group_barrier(0x2, LDPC_FAST64_STORE_VALU + FILLN, 0);   // VALU: compare, selects, sign merge, address (+ the filler's)
             __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);   // DS write: this edge's store
         }
     }
@@ -179,10 +266,18 @@ __device__ __forceinline__ bool cn_fast64(const Pack<double, 1> (&xin)[DCA], Pac
 
 // LDS byte address of 16-bit entry k of a packed schedule row: base + 8 * entry,
 // one v_mad_u32_u16 (op_sel picks the high half) instead of extract + shift-add.
-template <int DC>
+// SB: base is wave-uniform and is read from an SGPR (no VGPR copy of it to keep or re-materialise).
+template <int DC, bool SB = false>
 __device__ __forceinline__ uint32_t addr8(const uint32_t (&w)[DC / 2], int k, uint32_t base)
 {
     uint32_t a;
+    if constexpr (SB) {
+        if (k & 1)
+            asm("v_mad_u32_u16 %0, %1, 8, %2 op_sel:[1,0,0,0]" : "=v"(a) : "v"(w[k >> 1]), "s"(base));
+        else
+            asm("v_mad_u32_u16 %0, %1, 8, %2" : "=v"(a) : "v"(w[k >> 1]), "s"(base));
+        return a;
+    }
     if (k & 1)
         asm("v_mad_u32_u16 %0, %1, 8, %2 op_sel:[1,0,0,0]" : "=v"(a) : "v"(w[k >> 1]), "v"(base));
     else

@@ -132,6 +132,13 @@ __device__ __forceinline__ void padd(Pack<F, C> &s, const Pack<F, C> &r)
 #ifndef LDPC_VN_U1
 #define LDPC_VN_U1 4
 #endif
+// fp64 slots: a translation unit may set its own depths (rows_pp.hip does); default: the above
+#ifndef LDPC_VN_U3_F64
+#define LDPC_VN_U3_F64 LDPC_VN_U3
+#endif
+#ifndef LDPC_VN_U1_F64
+#define LDPC_VN_U1_F64 LDPC_VN_U1
+#endif
 #ifndef LDPC_VN_PIPE
 #define LDPC_VN_PIPE 0
 #endif
@@ -162,7 +169,8 @@ __device__ __forceinline__ void vn_phase(const Pack<F, C> *c2v, const int (&base
 {
     (void)lim;
     (void)site;
-    constexpr int U = NACT >= 3 ? LDPC_VN_U3 : LDPC_VN_U1;   // packs in flight per step: U * NACT
+    constexpr int U = sizeof(F) == 8 ? (NACT >= 3 ? LDPC_VN_U3_F64 : LDPC_VN_U1_F64)
+                                     : (NACT >= 3 ? LDPC_VN_U3 : LDPC_VN_U1);   // packs in flight per step: U * NACT
     if constexpr (LDPC_VN_PIPE) {
         // two steps in flight: step s+1's reads are issued before step s is added
         int n = (kend - k) / U;   // wave-uniform

@@ -45,6 +45,25 @@
 // position of both rows' check nodes; the two scatters, the bit role's two reads and its
 // app write are not issued. The thread also forms the bit's decision, error weight and
 // share of both rows' syndrome from the final prev. Same values, same order of additions.
+// The fp64 bit role's read depth (minsum_common.h vn_phase: edges in flight per step with >= 3
+// / < 3 active slots). 2 / 4 was the optimum while the check role was longer;
+// re-measured with the shortened check stream, 4 / 8 is faster on the bench instance;
+// it holds for every fp64 instance of this file. A build that sets the older switches
+// (-DLDPC_VN_U3 / -DLDPC_VN_U1, the A/B recipes of DESIGN §5b) sets the fp64 depths with them.
+#ifndef LDPC_VN_U3_F64
+#ifdef LDPC_VN_U3
+#define LDPC_VN_U3_F64 LDPC_VN_U3
+#else
+#define LDPC_VN_U3_F64 4
+#endif
+#endif
+#ifndef LDPC_VN_U1_F64
+#ifdef LDPC_VN_U1
+#define LDPC_VN_U1_F64 LDPC_VN_U1
+#else
+#define LDPC_VN_U1_F64 8
+#endif
+#endif
 #include "kernels.h"
 #include "device_common.h"
 #include "minsum_common.h"
@@ -151,6 +170,35 @@ namespace {
 // 11.42-11.44 (1) against 11.52-11.54 ms (0) per bench launch.
 #ifndef LDPC_PP_INREG_Y
 #define LDPC_PP_INREG_Y 1
+#endif
+// fp64 check role, N > 0: row 1's front (its v2c subtractions, two-min tournament and sign
+// parity: fast64.h CnFront64) is issued inside row 0's per-edge store chain, N operations
+// behind each of row 0's edges in source order and in that edge's pinned VALU group
+// (LDPC_PP_STORE_ORDER), so that they fill the compare -> select wait states; what is left of
+// the front, and the rest of row 1, stays behind the row fence. 0: row 1 follows row 0 whole.
+// Same operations on the same operands. Measured: DESIGN §5g.
+#ifndef LDPC_PP_ILV
+#define LDPC_PP_ILV 2
+#endif
+// LDPC_PP_ILV: row 0's first edges that take no operation of row 1 (their stores issue as early as without it)
+#ifndef LDPC_PP_ILV_SKIP
+#define LDPC_PP_ILV_SKIP 0
+#endif
+// 1: the check role's address arithmetic reads the slot's app / c2v base from an SGPR
+// (fast64.h addr8 SB) and the fp64 reciprocal of alpha lives in an SGPR pair; 0: VGPR copies.
+#ifndef LDPC_PP_SBASE
+#define LDPC_PP_SBASE 0
+#endif
+// fp64 premise flag (LDPC_PP_STICKY 0), 1: row 0's hi-word maximum is carried into row 1's
+// (fast64.h ACC takes the maximum) and tested once per interval, after row 1; both rows flag
+// the same slot, so the same codewords are re-decoded. 0: one test per row.
+#ifndef LDPC_PP_ONEPREM
+#define LDPC_PP_ONEPREM 1
+#endif
+#if LDPC_PP_SBASE && !defined(LDPC_CHECK)
+#define PP_ADDR8(DC, w, k, base, n, site) addr8<DC, true>(w, k, base)
+#else
+#define PP_ADDR8(DC, w, k, base, n, site) LDPC_ADDR8(DC, w, k, base, n, site)
 #endif
 
 // Diagnostic builds (-DLDPC_STAMPS, `make ppvariant`): per wave, s_memtime cycles
@@ -591,7 +639,10 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         }
     }
     auto vdst = [&](int i) -> int { return (int)((vdst2[i / 2] >> (16 * (i & 1))) & 0xffffu); };
-    const F alpha = (F)a.alpha, delta = (F)a.delta, rcp = F64 ? (F)(1.0 / a.alpha) : (F)a.alpha_rcp;
+    const F alpha = (F)a.alpha, delta = (F)a.delta;
+    F rcp = F64 ? (F)(1.0 / a.alpha) : (F)a.alpha_rcp;
+    if constexpr (F64 && LDPC_PP_SBASE && R > 0)   // the quotient of the f64 division sits in a VGPR pair: to SGPRs
+        rcp = mkd((uint32_t)__builtin_amdgcn_readfirstlane((int)lo32(rcp)), (uint32_t)__builtin_amdgcn_readfirstlane((int)hi32(rcp)));
     const int nsteps = (a.batch + 2 * C - 1) / (2 * C);
     if constexpr (HB && LDPC_PP_NOB2) {   // sentinels (never overwritten): padding edges gather +inf, rows past M +0
         P inf, zero;
@@ -783,7 +834,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 #pragma unroll
                         for (int k = 0; k < DCr - (IR == 1 && (r == 1 || YREG) ? 1 : 0); ++k)   // IR == 1: row 1's last edge is row 0's
                             xin[r][k] = lds_at<P>((LDPC_PP_EXP == 5 || LDPC_PP_EXP == 7) ? ab + 8u * (uint32_t)(lane + 64 * (k + 8 * r))
-                                                                                         : LDPC_ADDR8(DCX, colw[r], k, ab, N + 3, CHK_PP_GATHER));
+                                                                                         : PP_ADDR8(DCX, colw[r], k, ab, N + 3, CHK_PP_GATHER));
                     });
                     if constexpr (LDPC_PP_GATHER_FIRST && LDPC_PP_PREFETCH) {
                         // every gather of the interval issued ahead of the check-node arithmetic
@@ -821,6 +872,11 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                             xin[RR - 1][L1].v[c] = has ? sum.v[c] : xin[RR - 1][L1].v[c];
                         }
                     }
+                    // LDPC_PP_ILV: row 1's front, issued in row 0's store chain (ILV steps per edge of row 0)
+                    constexpr int ILV = (F64 && R == 2 && LDPC_PP_PREFETCH && LDPC_PP_STORE_ORDER && LDPC_PP_EXP == 0) ? LDPC_PP_ILV : 0;
+                    using Front = std::conditional_t<(ILV > 0), CnFront64<DC1>, int>;
+                    [[maybe_unused]] Front fr;
+                    [[maybe_unused]] uint32_t pa1 = 0;   // LDPC_PP_ONEPREM: the interval's premise maximum
                     static_for<0, R>([&](auto rc) {
                         constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
                         if (!LDPC_PP_PREFETCH && r > 0) {
@@ -834,7 +890,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                             if constexpr (LDPC_PP_EXP != 4)
                                 lds_put<P>((LDPC_PP_EXP == 6 || LDPC_PP_EXP == 7)
                                                ? cb + 8u * (uint32_t)(lane + 64 * ((k + 8 * r + 16 * (tid >> 6)) % 112))
-                                               : LDPC_ADDR8(DCX, posw[r], k, cb, EA, CHK_PP_SCATTER),
+                                               : PP_ADDR8(DCX, posw[r], k, cb, EA, CHK_PP_SCATTER),
                                            m);
                         };
                         if constexpr (LDPC_PP_EXP == 3) {
@@ -845,11 +901,33 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                                 store(k, prev[X][r][k]);
                             }
                         } else {
-                            [[maybe_unused]] uint32_t pa = 0;
-                            ok = pp_check_node<F, DCr, VAR, FDIV>(xin[r], prev[X][r], alpha, rcp, delta, store,
-                                                                  LDPC_PP_STICKY ? &pacc[X] : &pa);
-                            if constexpr (F64 && !LDPC_PP_STICKY) {
-                                // rare: M2 >= 2^1000 (inf, NaN) or a tiny minimum in this row
+                            constexpr bool ONE = F64 && !LDPC_PP_STICKY && LDPC_PP_ONEPREM && R == 2;
+                            [[maybe_unused]] uint32_t pa0 = 0;
+                            uint32_t &pa = ONE ? pa1 : pa0;
+                            if constexpr (ILV > 0) {
+                                constexpr int NF = Front::N, SK = LDPC_PP_ILV_SKIP, CUT = ILV * (DC0 - SK) < NF ? ILV * (DC0 - SK) : NF;
+                                if constexpr (r == 0) {
+                                    // steps ILV (k - SK) .. + ILV - 1 of row 1's front behind row 0's edge k (k a constant once inlined)
+                                    auto fill = [&](int k) {
+                                        static_for<0, CUT>([&](auto ic) {
+                                            constexpr int I = decltype(ic)::value;
+                                            if (I / ILV + SK == k) fr.template step<I>(xin[1], prev[X][1]);
+                                        });
+                                    };
+                                    ok = cn_fast64<DCr, VAR, FDIV, DCX, decltype(store), true, true, decltype(fill), ILV>(
+                                        xin[r], prev[X][r], alpha, rcp, delta, store, LDPC_PP_STICKY ? &pacc[X] : &pa, fill);
+                                } else {
+                                    static_for<CUT, NF>([&](auto ic) { fr.template step<decltype(ic)::value>(xin[1], prev[X][1]); });
+                                    ok = cn_fast64_back<DCr, VAR, FDIV, DCX, decltype(store), true, true>(
+                                        fr.x, fr.mn1, fr.mn2, fr.par, prev[X][r], alpha, rcp, delta, store,
+                                        LDPC_PP_STICKY ? &pacc[X] : &pa);
+                                }
+                            } else {
+                                ok = pp_check_node<F, DCr, VAR, FDIV>(xin[r], prev[X][r], alpha, rcp, delta, store,
+                                                                      LDPC_PP_STICKY ? &pacc[X] : &pa);
+                            }
+                            if constexpr (F64 && !LDPC_PP_STICKY && (!ONE || r == R - 1)) {
+                                // rare: M2 >= 2^1000 (inf, NaN) or a tiny minimum in this row (ONE: in either row)
                                 if (__builtin_amdgcn_ballot_w64(pa >= kFast64MaxHi)) {
                                     asm volatile(";");   // a side effect: stays a skipped branch
                                     if (pa >= kFast64MaxHi && LDPC_PP_EXP == 0) s.red[X] = 1;

@@ -325,6 +325,8 @@ _SIG = {
     "ldpc_ctx_last_kernel_ms": ([_vp, C.POINTER(C.c_float)], _i32),
     "ldpc_ctx_kernel_info": (_info(_Cfg) + [_pi32], _i32),
     "ldpc_ctx_redo_count": ([_vp, C.POINTER(C.c_int64)], _i32),
+    "ldpc_ctx_redo_list": ([_vp, _vp, C.c_int64, C.POINTER(C.c_int64)], _i32),
+    "ldpc_ctx_pp_row_slots": ([_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)], _i32),
     "ldpc_ctx_row_sched_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
     "ldpc_ctx_pp_inreg_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
     "ldpc_ctx_set_option": ([_vp, _i32, _i32], _i32),
@@ -372,7 +374,7 @@ _lib = None
 
 
 # exports added without an ABI bump: the product library has them, an older A/B build may not
-_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info"}
+_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_redo_list", "ldpc_ctx_pp_row_slots"}
 
 
 def lib():
@@ -627,6 +629,13 @@ class Context:
         _check(lib().ldpc_ctx_redo_count(self._h, C.byref(n)))
         return int(n.value)
 
+    def redo_list(self) -> np.ndarray:
+        """Batch indices of those codewords, sorted (the kernel lists them in any order)."""
+        n = C.c_int64()
+        out = np.zeros(max(self.redo_count(), 1), dtype=np.uint32)
+        _check(lib().ldpc_ctx_redo_list(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return np.sort(out[:int(n.value)])
+
     def row_sched_info(self, cfg: DecoderConfig) -> dict:
         """Shape of the row kernel that decodes cfg (raises LdpcError UNSUPPORTED for other kernels)."""
         info = np.zeros(10, dtype=np.int32)
@@ -641,6 +650,15 @@ class Context:
         _check(lib().ldpc_ctx_pp_inreg_info(self._h, C.byref(cfg._c()), info.ctypes.data))
         keys = ("inreg_bits", "lds_check_edges", "bit_slot_edges", "slots_per_thread")
         return {k: int(v) for k, v in zip(keys, info)}
+
+    def pp_row_slots(self, cfg: DecoderConfig):
+        """(cols [slots, 8] uint16, deg [slots] uint8) of the schedule the ping-pong kernel runs cfg on, from
+        the device: slot j is row j // threads of check thread j % threads; entries >= N are padding edges."""
+        cols = np.zeros((2048, 8), dtype=np.uint16)
+        deg = np.zeros(2048, dtype=np.uint8)
+        n = C.c_int()
+        _check(lib().ldpc_ctx_pp_row_slots(self._h, C.byref(cfg._c()), cols.ctypes.data, deg.ctypes.data, 2048, C.byref(n)))
+        return cols[:n.value], deg[:n.value]
 
     def kernel_info(self, cfg: DecoderConfig) -> dict:
         name = C.create_string_buffer(32)
