@@ -28,6 +28,10 @@
  *     GDBF / NGDBF bit-flipping decoders (src/decodeGDBF.cpp:250-399,
  *     checkNodeUpdates :517-534, symNodeUpdates :536-621), whose -D switches
  *     (Makefile:33-53) are the flags of ldpc_gdbf_cfg.
+ *   - ldpc_fxms_decode_batch / ldpc_fxms_sim_* stand where ldpc_decode_batch /
+ *     ldpc_sim_* do, for min-sum with integer messages of a chosen width (no
+ *     reference program has them: its -D quantizeSamples quantises the samples
+ *     only, src/decodeMinSum.cpp:480-489).
  *   - ldpc_nb_* / ldpc_ems_* (ABI 5): non-binary GF(16) codes (BASELINE
  *     config 5). ldpc_nb_graph_create / _load_alist replace the NB-LDPC
  *     model's loadFile() (SystemC/NB-LDPC/src/alist.cpp:23-56,
@@ -573,6 +577,74 @@ int  ldpc_hwgdbf_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_h
  * workgroup per codeword; the library takes the one that keeps more waves on a CU, and
  * option LDPC_OPT_GDBF_KERNEL at 1 forces hwgdbf_wg) and the LDS bytes of a workgroup. The cfg is checked first, also with a NULL context. */
 int  ldpc_hwgdbf_kernel_info(ldpc_ctx *ctx, const ldpc_hwgdbf_cfg *cfg, char *name, int name_len, int *lds_bytes);
+
+/* ---- fixed-point min-sum (fxms) ----------------------------------------- */
+/* Flooding MS / NMS / OMS whose messages are msg_bits-wide saturating integers,
+ * as a hardware min-sum decoder has them (the reference's min-sum programs only
+ * quantise the channel samples, -D quantizeSamples; its messages stay double).
+ * With Nq = 2^qbits, V = 2^(msg_bits - 1) - 1 and sgn(x) = x >= 0 ? +1 : -1
+ * (decodeMinSum.cpp:518-523):
+ *   front end  in `precision` (ymax rounded to it once), quantize() of
+ *              decodeMinSum.cpp:480-489 in its order of operations, as an integer
+ *              code: a = |y|, s = sgn(y); a > ymax: Y = s (Nq - 1); else
+ *              Y = s 2 max(floor(a (Nq - 1) / (2 ymax)), 1). Y is never 0 and odd
+ *              only when saturated. For ymax = (Nq - 1) 2^-s, Y 2^-s is the
+ *              quantised sample of ldpc_decoder_cfg.quantize exactly. The uncoded
+ *              decision is r = Y > 0 ? +1 : -1.
+ *   start      v2c = clamp(Y_i, -V, V) on every edge of bit i.
+ *   check j    P = prod sgn(v2c) over the row, m1 <= m2 the two smallest |v2c|
+ *              (V where the row has fewer edges); for edge k, mag = m2 at the
+ *              position of the minimum, else m1; MS: as is; NMS:
+ *              (mag * nms_num) >> nms_shift; OMS: max(mag - beta, 0);
+ *              c2v_k = P sgn(v2c_k) mag.
+ *   bit i      S_i = Y_i + sum c2v in int32 (the unclamped Y_i);
+ *              v2c_k = clamp(S_i - c2v_k, -V, V); d_i = S_i > 0 ? +1 : -1.
+ * T flooding iterations (T = 0: d = r); early_stop as ldpc_decoder_cfg.early_stop
+ * (the result is D(s) for the smallest s in 0..T with a zero syndrome, s = T when
+ * there is none; frames[].iters = s and counts->iters += s; without it
+ * frames[].iters = 0 and counts->iters += T). Everything after the front end is
+ * integer, so results are exact on every kernel shape, and a decoder whose messages
+ * never saturate reproduces fp64 MS / OMS on grid samples bit for bit.
+ * A codeword's state -- the messages of maxdc * M slots (one byte each for
+ * msg_bits <= 8, else two) and 2 N bytes -- lives in LDS: a graph where it exceeds
+ * 65536 bytes is LDPC_ERR_UNSUPPORTED (DVB-S2 is out of scope: no global-memory
+ * kernel). No reference program computes this decoder. */
+typedef struct {
+    int32_t variant;     /* LDPC_MS | LDPC_NMS | LDPC_OMS; another ldpc_variant: LDPC_ERR_UNSUPPORTED */
+    int32_t precision;   /* front end only */
+    int32_t T;           /* >= 0 */
+    int32_t qbits;       /* 2..7  (|Y| <= 127) */
+    int32_t msg_bits;    /* 2..16 */
+    int32_t nms_num;     /* NMS: 1 <= nms_num <= 2^nms_shift */
+    int32_t nms_shift;   /* NMS: 0..7 */
+    int32_t beta;        /* OMS: >= 0 */
+    int32_t early_stop;
+    int32_t reserved;    /* 0 */
+    double  ymax;        /* > 0 */
+} ldpc_fxms_cfg;
+
+/* Decode `batch` frames of given raw channel samples y[batch][N] (float for F32,
+ * double for F64); every argument as ldpc_decode_batch. Synchronous. */
+int  ldpc_fxms_decode_batch(ldpc_ctx *ctx, const void *y, int batch, const ldpc_fxms_cfg *cfg, const int8_t *c,
+                            int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts);
+/* Fused on-device Monte-Carlo of one SNR point: the channel of frame f is the
+ * min-sum path's for the same (seed, stream_id, frame), the codeword table of
+ * ldpc_sim_set_codewords applies. Asynchronous; counts accumulate in the context. */
+int  ldpc_fxms_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev);
+/* ldpc_fxms_sim_launch + counts accumulated into *accum; frames host or device. Synchronous. */
+int  ldpc_fxms_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                         ldpc_counts *accum);
+/* ldpc_fxms_sim_batch that also returns the raw samples drawn, y_out[batch][N] (the
+ * cfg's precision; ldpc_sim_trace's bit for bit), the integer codes
+ * ycode_out[batch][N] and d_out (host or device; any may be NULL). */
+int  ldpc_fxms_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out,
+                         int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *accum);
+/* Kernel chosen for a cfg ("fxms_i8": one-byte messages, msg_bits <= 8; "fxms_i16")
+ * and the LDS bytes of a workgroup. The cfg is checked first, also with a NULL context. */
+int  ldpc_fxms_kernel_info(ldpc_ctx *ctx, const ldpc_fxms_cfg *cfg, char *name, int name_len, int *lds_bytes);
 
 /* ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ------ */
 /* Messages are reliabilities over GF(q) (0 = most likely symbol); check

@@ -10,6 +10,7 @@
 #include "rgdbf.h"
 #include "rstat.h"
 #include "hwgdbf.h"
+#include "fxms.h"
 #include "bp.h"
 #include "ddbmp.h"
 #include "nb.h"
@@ -45,7 +46,8 @@ static const char *check_site_name(unsigned s)
         "EMS message slot", "bp_rows bit", "bp_rows message slot", "ddbmp edge flag slot", "ddbmp check parity",
         "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
         "hwgdbf noise sample", "rstat decision byte", "rstat check parity", "rows_es gather (app entry)",
-        "rows_es scatter (c2v slot)", "rows_es bit read (c2v slot)", "rows_es app write"};
+        "rows_es scatter (c2v slot)", "rows_es bit read (c2v slot)", "rows_es app write", "fxms message slot",
+        "fxms decision byte"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -54,7 +56,8 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     if (e != hipSuccess) return -(long)e;
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
-                                              check_take_rgdbf, check_take_hwgdbf, check_take_rstat, check_take_rows_es};
+                                              check_take_rgdbf, check_take_hwgdbf, check_take_rstat, check_take_rows_es,
+                                              check_take_fxms};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -75,6 +78,7 @@ struct ldpc_ctx : CtxCore {
     DevBuf graph, hist, y_stage, c_stage, d_stage, fw_stage, cw_table, gscratch, p_stage;
     DevBuf rs_att_stage, rs_unc, rs_tr_stage[4];          // every-attempt decoders: attempt results, uncoded errors, traces
     DevBuf hw_ptr_stage, hw_it_stage;                     // NGDBFhw: start pointers in, iterations run out
+    DevBuf fx_code_stage;                                 // fixed-point min-sum: the integer codes out
     int cw_rows = 0;
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
     bool has_rs = false;
@@ -402,7 +406,7 @@ static void ctx_free(ldpc_ctx *c)
     if (!c) return;
     c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
                 &c->sched, &c->sched_pp, &c->sched_ppi, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
-                &c->hw_ptr_stage, &c->hw_it_stage, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
+                &c->hw_ptr_stage, &c->hw_it_stage, &c->fx_code_stage, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
                 &c->rs_tr_stage[2], &c->rs_tr_stage[3]});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
     if (c->aux.join) (void)hipEventDestroy(c->aux.join);
@@ -1479,6 +1483,142 @@ int ldpc_hwgdbf_kernel_info(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, char *name,
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     ldpc::HwgdbfChoice ch;
     RC_TRY(hwgdbf_pick(c, cfg, ch));
+    return report_choice(ch, name, name_len, lds_bytes);
+}
+
+// ----------------------------------------------------------------- fixed-point min-sum
+static int fxms_check_cfg(const ldpc_fxms_cfg *cfg)
+{
+    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
+    if (cfg->variant != LDPC_MS && cfg->variant != LDPC_NMS && cfg->variant != LDPC_OMS)
+        return set_err(cfg->variant == LDPC_BP || cfg->variant == LDPC_DDBMP ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_INVALID,
+                       "variant %d: fixed-point min-sum is MS, NMS or OMS", cfg->variant);
+    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
+        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
+    if (cfg->reserved != 0) return set_err(LDPC_ERR_INVALID, "reserved must be 0");
+    if (cfg->T < 0) return set_err(LDPC_ERR_INVALID, "T must be >= 0");
+    if (cfg->qbits < 2 || cfg->qbits > 7) return set_err(LDPC_ERR_INVALID, "qbits must be in 2..7");
+    if (cfg->msg_bits < 2 || cfg->msg_bits > 16) return set_err(LDPC_ERR_INVALID, "msg_bits must be in 2..16");
+    if (cfg->variant == LDPC_NMS) {
+        if (cfg->nms_shift < 0 || cfg->nms_shift > 7) return set_err(LDPC_ERR_INVALID, "nms_shift must be in 0..7");
+        if (cfg->nms_num < 1 || cfg->nms_num > (1 << cfg->nms_shift))
+            return set_err(LDPC_ERR_INVALID, "nms_num must be in 1..2^nms_shift = %d", 1 << cfg->nms_shift);
+    }
+    if (cfg->variant == LDPC_OMS && cfg->beta < 0) return set_err(LDPC_ERR_INVALID, "beta must be >= 0");
+    if (cfg->early_stop != 0 && cfg->early_stop != 1) return set_err(LDPC_ERR_INVALID, "early_stop must be 0 or 1");
+    if (!(cfg->ymax > 0) || !std::isfinite(cfg->ymax)) return set_err(LDPC_ERR_INVALID, "ymax must be > 0");
+    return LDPC_OK;
+}
+
+// The kernel instance for cfg->msg_bits on the context's graph, or the refusal when one codeword's state exceeds LDS.
+static int fxms_pick(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, ldpc::FxmsChoice &ch)
+{
+    ch = ldpc::fxms_choose(c->dg, c->g->E, cfg->msg_bits);
+    if (!ch.name[0])
+        return set_err(LDPC_ERR_UNSUPPORTED,
+                       "fixed-point min-sum keeps a codeword in LDS: maxdc * M messages + 2 N = %d bytes exceed the "
+                       "bound of %d",
+                       ch.cw_bytes, ldpc::kFxmsMaxLds);
+    return LDPC_OK;
+}
+
+// Host work only (its refusals come before enter()).
+static int fxms_fill(ldpc::FxmsArgs &a, ldpc::FxmsChoice &ch, ldpc_ctx *c, const ldpc_fxms_cfg *cfg, int batch)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.variant = cfg->variant;   // LDPC_MS / NMS / OMS are V_MS / V_NMS / V_OMS
+    a.nq1 = (1 << cfg->qbits) - 1;
+    a.vmax = (1 << (cfg->msg_bits - 1)) - 1;
+    a.nms_num = cfg->nms_num;
+    a.nms_shift = cfg->nms_shift;
+    a.beta = cfg->beta;
+    a.early_stop = cfg->early_stop;
+    a.ymax = cfg->ymax;
+    fill_accounting(a, *c);
+    return fxms_pick(c, cfg, ch);
+}
+
+static int fxms_run(ldpc_ctx *c, const ldpc::FxmsArgs &a, const ldpc::FxmsChoice &ch, bool f64)
+{
+    RC_TRY(c->begin_launch());
+    HIP_TRY(ldpc::fxms_launch(c->dg, a, f64, ch, c->g->E, c->num_cus, c->stream));
+    return c->end_launch();
+}
+
+int ldpc_fxms_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_fxms_cfg *cfg, const int8_t *cw,
+                           int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+{
+    if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(fxms_check_cfg(cfg));
+    RC_TRY(check_batch(*c, batch));
+    ldpc::FxmsArgs a;
+    ldpc::FxmsChoice ch;
+    RC_TRY(fxms_fill(a, ch, c, cfg, batch));
+    RC_TRY(c->enter());
+    const bool f64 = cfg->precision == LDPC_F64;
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, nullptr, 0, nullptr, cw));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
+    RC_TRY(fxms_run(c, a, ch, f64));
+    return s.finish(counts);
+}
+
+// The refusals of the ldpc_fxms_sim_* calls that need no device, and the launch arguments of cfg.
+static int fxms_sim_setup(ldpc_ctx *c, const SimCall &q, const ldpc_fxms_cfg *cfg, ldpc::FxmsArgs &a, ldpc::FxmsChoice &ch)
+{
+    RC_TRY(check_sim(c, [&] { return fxms_check_cfg(cfg); }, q, false));
+    RC_TRY(fxms_fill(a, ch, c, cfg, q.batch));
+    fill_sim(a, *c, q);
+    fill_cw_table(a, *c);
+    return LDPC_OK;
+}
+
+int ldpc_fxms_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    ldpc::FxmsArgs a;
+    ldpc::FxmsChoice ch;
+    RC_TRY(fxms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    a.frame_res = (int4 *)frames_dev;
+    return fxms_run(c, a, ch, cfg->precision == LDPC_F64);
+}
+
+int ldpc_fxms_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                        uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out, int8_t *d_out,
+                        ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    ldpc::FxmsArgs a;
+    ldpc::FxmsChoice ch;
+    RC_TRY(fxms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    RC_TRY(c->enter());
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    const size_t nb = (size_t)batch * c->g->N;
+    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), a.y_out));
+    RC_TRY(s.out(ycode_out, c->fx_code_stage, nb, a.ycode_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(fxms_run(c, a, ch, cfg->precision == LDPC_F64));
+    return s.finish(accum);
+}
+
+int ldpc_fxms_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                        uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    return ldpc_fxms_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames,
+                               accum);
+}
+
+int ldpc_fxms_kernel_info(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, char *name, int name_len, int *lds_bytes)
+{
+    RC_TRY(fxms_check_cfg(cfg));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    ldpc::FxmsChoice ch;
+    RC_TRY(fxms_pick(c, cfg, ch));
     return report_choice(ch, name, name_len, lds_bytes);
 }
 

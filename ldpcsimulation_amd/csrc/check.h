@@ -49,6 +49,8 @@ enum CheckSite : unsigned {
     CHK_ES_SCATTER,        // rows_es: c2v slot of a check row's edge       (< e_pad + 64)
     CHK_ES_BIT_READ,       // rows_es: c2v slot a bit slot reads            (< e_pad + 64)
     CHK_ES_APP_WRITE,      // rows_es: app entry a bit slot writes          (< N + 2)
+    CHK_FXMS_SLOT,         // fxms: message slot of a check / bit edge      (< maxdc * M)
+    CHK_FXMS_BIT,          // fxms: decision byte a check gathers           (< N)
     CHK_SITES
 };
 
@@ -114,6 +116,7 @@ hipError_t check_take_rgdbf(CheckRec *out);
 hipError_t check_take_hwgdbf(CheckRec *out);
 hipError_t check_take_rstat(CheckRec *out);
 hipError_t check_take_rows_es(CheckRec *out);
+hipError_t check_take_fxms(CheckRec *out);
 #endif
 
 }  // namespace ldpc

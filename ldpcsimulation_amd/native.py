@@ -220,6 +220,33 @@ class HwGdbfConfig:
                           self.noise_scale, self.theta0)
 
 
+class _FxmsCfg(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("precision", C.c_int32), ("T", C.c_int32), ("qbits", C.c_int32),
+                ("msg_bits", C.c_int32), ("nms_num", C.c_int32), ("nms_shift", C.c_int32), ("beta", C.c_int32),
+                ("early_stop", C.c_int32), ("reserved", C.c_int32), ("ymax", C.c_double)]
+
+
+@dataclass
+class FxmsConfig:
+    """Fixed-point min-sum (include/ldpc_hip.h ldpc_fxms_cfg): integer samples of qbits bits,
+    saturating integer messages of msg_bits bits, NMS as (m * nms_num) >> nms_shift, OMS as
+    max(m - beta, 0). The precision is the front end's only."""
+    variant: int = MS
+    T: int = 10
+    qbits: int = 5
+    msg_bits: int = 6
+    nms_num: int = 3
+    nms_shift: int = 2
+    beta: int = 1
+    early_stop: bool = False
+    ymax: float = 31 / 16
+    precision: int = F64
+
+    def _c(self) -> _FxmsCfg:
+        return _FxmsCfg(self.variant, self.precision, self.T, self.qbits, self.msg_bits, self.nms_num, self.nms_shift,
+                        self.beta, int(self.early_stop), 0, self.ymax)
+
+
 def rgdbf_phases(iters, T: int, maxphase: int):
     """Phases a frame ran, from its total iterations (int or array): a failed phase runs
     exactly T iterations and a satisfied one fewer, so phases = min(maxphase, iters // T + 1)."""
@@ -353,6 +380,11 @@ _SIG = {
     "ldpc_hwgdbf_sim_batch": (_sim(_HwGdbfCfg, _vp, C.POINTER(Counts)), _i32),
     "ldpc_hwgdbf_sim_trace": (_sim(_HwGdbfCfg, _vp, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
     "ldpc_hwgdbf_kernel_info": (_info(_HwGdbfCfg), _i32),
+    "ldpc_fxms_decode_batch": ([_vp, _vp, _i32, C.POINTER(_FxmsCfg), _vp, _vp, _vp, C.POINTER(Counts)], _i32),
+    "ldpc_fxms_sim_launch": (_sim(_FxmsCfg, _vp), _i32),
+    "ldpc_fxms_sim_batch": (_sim(_FxmsCfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_fxms_sim_trace": (_sim(_FxmsCfg, _vp, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_fxms_kernel_info": (_info(_FxmsCfg), _i32),
     "ldpc_nb_graph_create": ([_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)], _i32),
     "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(_vp)], _i32),
     "ldpc_nb_graph_info": ([_vp] + [_pi32] * 6, _i32),
@@ -374,7 +406,8 @@ _lib = None
 
 
 # exports added without an ABI bump: the product library has them, an older A/B build may not
-_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_redo_list", "ldpc_ctx_pp_row_slots"}
+_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_redo_list", "ldpc_ctx_pp_row_slots", "ldpc_fxms_decode_batch",
+                 "ldpc_fxms_sim_launch", "ldpc_fxms_sim_batch", "ldpc_fxms_sim_trace", "ldpc_fxms_kernel_info"}
 
 
 def lib():
@@ -831,6 +864,37 @@ class Context:
 
     def hwgdbf_kernel_info(self, cfg: HwGdbfConfig) -> dict:
         return _kernel_info(lib().ldpc_hwgdbf_kernel_info, self._h, C.byref(cfg._c()))
+
+    # ---- fixed-point min-sum (integer messages) ----
+    def fxms_decode(self, y, cfg: FxmsConfig, c=None, want_decisions: bool = True):
+        """Decode raw channel samples y[batch, N]. Returns (d, frames, Counts); frames' iters are
+        0, or with early_stop the iteration whose decisions are returned."""
+        y, batch, c, _ = _given(self.graph.N, cfg, y, c)
+        return self._decode(lib().ldpc_fxms_decode_batch, y, cfg, c, want_decisions)
+
+    def fxms_sim_launch(self, ebn0_db: float, R: float, cfg: FxmsConfig, seed: int, stream_id: int, first_cw: int,
+                        batch: int, frames_dev=None):
+        _sim_launch(lib().ldpc_fxms_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
+
+    def fxms_sim_batch(self, ebn0_db: float, R: float, cfg: FxmsConfig, seed: int, stream_id: int, first_cw: int,
+                       batch: int, want_frames: bool = True):
+        return _sim_batch(lib().ldpc_fxms_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
+
+    def fxms_sim_trace(self, ebn0_db: float, R: float, cfg: FxmsConfig, seed: int, stream_id: int, first_cw: int,
+                       batch: int):
+        """fxms_sim_batch that also returns the samples drawn and their integer codes:
+        (y, ycode, d, frames, Counts)."""
+        N = self.graph.N
+        y = np.empty((batch, N), dtype=np.float64 if cfg.precision == F64 else np.float32)
+        code = np.empty((batch, N), dtype=np.int8)
+        d = np.empty((batch, N), dtype=np.int8)
+        fr, cnt = _sim_batch(lib().ldpc_fxms_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                             y, code, d)
+        return y, code, d, fr, cnt
+
+    def fxms_kernel_info(self, cfg: FxmsConfig) -> dict:
+        return _kernel_info(lib().ldpc_fxms_kernel_info, self._h, C.byref(cfg._c()))
 
 
 # ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ----

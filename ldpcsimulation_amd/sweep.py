@@ -29,7 +29,10 @@ line for each point.
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 3.0 3.5 -T 100 --gdbf RSMNGDBF --alpha 0.96 --ymax 2.5 --maxphase 3
     # the fixed-point NGDBF hardware model (NGDBFhw; its constants are the defaults, R = 0.8413 on 802.3an)
     python -m ldpcsimulation_amd.sweep 802_3_H.alist --rate 0.8413 --snr 4.0 4.25 -T 600 --hwgdbf
-Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
+    # fixed-point min-sum: integer messages of --msg-bits bits, NMS as (m * NUM) >> SHIFT, OMS as max(m - B, 0)
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 50 --fxms --variant nms --scale 3 2 \\
+        --quantize 1.9375 5 --msg-bits 6 --early-stop
+Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (--fxms: SNR BER avgIt FER T Ymax Q msgBits [num shift] [beta] alist; DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
 BER over coded bits, 4 per GF(16) symbol; --gdbf: SNR BER avgIt FER T theta noiseScale lambda alpha windowsize Ymax
 [maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job;
 --hwgdbf: SNR BER avgIt FER T theta0 noiseScale w Ymax NQ maxphase qlen alist).
@@ -58,6 +61,8 @@ GDBF_DEFAULTS = {"theta": -0.6, "lam": 0.99, "noise_scale": 0.75, "window": 16, 
 # --hwgdbf settings left unset take these (NGDBFhw.cpp:48-57, native.HwGdbfConfig's)
 HWGDBF_DEFAULTS = {"w": 0.185, "ymax": 1.625, "noise_scale": 0.95, "theta0": -0.525, "nq": 5, "maxphase": 1,
                    "qlen": 2648}
+# --fxms settings left unset take these (--quantize YMAX Q, --msg-bits, --scale NUM SHIFT, --beta)
+FXMS_DEFAULTS = {"ymax": 31 / 16, "qbits": 5, "msg_bits": 6, "nms_num": 3, "nms_shift": 2, "beta": 1}
 
 
 def parse(argv=None):
@@ -99,6 +104,13 @@ def parse(argv=None):
     p.add_argument("--w", type=float, help="--hwgdbf: syndrome weight parameter w (default 0.185)")
     p.add_argument("--theta0", type=float, help="--hwgdbf: noise offset theta0 (default -0.525)")
     p.add_argument("--qlen", type=int, help="--hwgdbf: noise samples per frame, > N (default 2648)")
+    p.add_argument("--fxms", action="store_true",
+                   help="fixed-point min-sum (integer messages): --variant ms|nms|oms, --quantize YMAX Q (default 1.9375 5), "
+                        "-T, --precision (of the front end) and --early-stop are reused")
+    p.add_argument("--msg-bits", type=int, help="--fxms: message width in bits, 2..16 (default 6)")
+    p.add_argument("--scale", type=int, nargs=2, metavar=("NUM", "SHIFT"),
+                   help="--fxms --variant nms: magnitudes become (m * NUM) >> SHIFT (default 3 2)")
+    p.add_argument("--beta", type=int, help="--fxms --variant oms: magnitudes become max(m - B, 0) (default 1)")
     p.add_argument("--ems", action="store_true", help="GF(q) Extended Min-Sum on an NB alist (BASELINE config 5)")
     p.add_argument("--nm", type=int, default=16, help="EMS message truncation")
     p.add_argument("--offset", type=float, default=0.0, help="EMS fill offset")
@@ -127,6 +139,19 @@ def parse(argv=None):
     a = p.parse_args(argv)
     if a.early_stop and a.schedule == "layered":
         p.error("--early-stop is not supported with --schedule layered")
+    if a.fxms:
+        if a.gdbf or a.hwgdbf or a.ems or a.schedule != "flooding":
+            p.error("--fxms excludes --gdbf, --hwgdbf, --ems and --schedule layered")
+        if a.variant not in ("ms", "nms", "oms"):
+            p.error("--fxms is --variant ms, nms or oms")
+        if a.saturate is not None or a.ymax is not None or a.qbits is not None or a.alpha != 1.0 or a.delta != 0.0:
+            p.error("--fxms takes its settings from --quantize YMAX Q, --msg-bits, --scale NUM SHIFT and --beta")
+        if (a.scale is not None and a.variant != "nms") or (a.beta is not None and a.variant != "oms"):
+            p.error("--fxms: --scale belongs to --variant nms and --beta to --variant oms")
+    else:
+        for n in ("msg_bits", "scale", "beta"):
+            if getattr(a, n) is not None:
+                p.error("--" + n.replace("_", "-") + " belongs to --fxms")
     gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
     if a.hwgdbf:
         if a.gdbf or a.ems or a.schedule != "flooding" or a.variant != "ms":
@@ -170,6 +195,8 @@ def _checkpoint_config(a) -> dict:
         ddbmp = {"gdbf": a.gdbf, **_gdbf_settings(a)}
     if getattr(a, "hwgdbf", False):   # likewise
         ddbmp = {"hwgdbf": True, **_hwgdbf_settings(a)}
+    if getattr(a, "fxms", False):   # likewise: every field of the cfg, so another width is another sweep
+        ddbmp = {"fxms": True, **_fxms_settings(a)}
     if _min_sum_early_stop(a):   # likewise (the "early_stop" key below is the EMS setting)
         ddbmp = {**ddbmp, "min_sum_early_stop": True}
     return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
@@ -199,6 +226,20 @@ def _gdbf_settings(a) -> dict:
 def _hwgdbf_settings(a) -> dict:
     """The --hwgdbf settings with their defaults filled in."""
     return {k: (getattr(a, k) if getattr(a, k) is not None else v) for k, v in HWGDBF_DEFAULTS.items()}
+
+
+def _fxms_settings(a) -> dict:
+    """The --fxms settings with their defaults filled in."""
+    s = dict(FXMS_DEFAULTS)
+    if a.quantize:
+        s["ymax"], s["qbits"] = float(a.quantize[0]), int(a.quantize[1])
+    if a.msg_bits is not None:
+        s["msg_bits"] = a.msg_bits
+    if a.scale is not None:
+        s["nms_num"], s["nms_shift"] = a.scale
+    if a.beta is not None:
+        s["beta"] = a.beta
+    return s
 
 
 def _run_points(a, ck, rank, n_hist, run_point):
@@ -264,6 +305,8 @@ def main(argv=None) -> int:
         return _ems_sweep(a, seed, world, rank, device, ck)
     if a.gdbf or a.hwgdbf:
         return _gdbf_sweep(a, seed, world, rank, device, ck)
+    if a.fxms:
+        return _fxms_sweep(a, seed, world, rank, device, ck)
     cfg = native.DecoderConfig(variant=VARIANTS[a.variant], T=a.iterations, alpha=a.alpha, delta=a.delta,
                                precision=native.F64 if a.precision == "f64" else native.F32,
                                schedule=native.LAYERED if a.schedule == "layered" else native.FLOODING,
@@ -375,7 +418,7 @@ def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
         extra = [s["theta0"], s["noise_scale"], s["w"], s["ymax"], float(s["nq"]), float(s["maxphase"]),
                  float(s["qlen"])]
         return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra,
-                            "NGDBFhw")
+                            {"gdbf": "NGDBFhw"})
     s = _gdbf_settings(a)
     common = dict(T=a.iterations, theta=s["theta"], lambda_=s["lam"], alpha=a.alpha, noise_scale=s["noise_scale"],
                   ymax=s["ymax"], windowsize=s["window"], precision=prec)
@@ -388,12 +431,36 @@ def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
     extra = [s["theta"], s["noise_scale"], s["lam"], a.alpha, float(s["window"]), s["ymax"]]
     if a.gdbf == "RSMNGDBF":
         extra.append(float(s["maxphase"]))
-    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra, a.gdbf)
+    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra,
+                        {"gdbf": a.gdbf})
 
 
-def _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra, name) -> int:
-    """The points of a bit-flipping sweep: early stop, so the frames report their iterations."""
-    min_fe = a.min_frame_errors
+def _fxms_sweep(a, seed, world, rank, device, ck=None) -> int:
+    """One SNR point after the other on fixed-point min-sum, frames sharded as above; the min-sum
+    stop rule (decodeMinSum.cpp:189). With --early-stop the frames report their iterations."""
+    g = native.Graph.from_alist(a.alist)
+    ctx = native.Context(g, device, a.batch)
+    s = _fxms_settings(a)
+    cfg = native.FxmsConfig(variant=VARIANTS[a.variant], T=a.iterations, early_stop=bool(a.early_stop),
+                            precision=native.F64 if a.precision == "f64" else native.F32, **s)
+    extra = [s["ymax"], float(s["qbits"]), float(s["msg_bits"])]
+    if a.variant == "nms":
+        extra += [float(s["nms_num"]), float(s["nms_shift"])]
+    elif a.variant == "oms":
+        extra.append(float(s["beta"]))
+    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, ctx.fxms_sim_batch, ctx.fxms_sim_launch,
+                        ctx.fxms_kernel_info, extra, {"decoder": "fxms", "variant": a.variant, "schedule": a.schedule},
+                        stops=cfg.early_stop,
+                        min_fe=a.min_frame_errors if a.min_frame_errors is not None else 40)
+
+
+def _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch_fn, info_fn, extra, family, stops=True,
+                 min_fe=None) -> int:
+    """The points of a sweep of one of the ticket families. stops: the decoder stops early, so the
+    frames report their iterations (the bit-flipping decoders always do). min_fe: None = the GDBF
+    family's stop rule. family: the keys of the JSON line that name the decoder."""
+    if min_fe is None:
+        min_fe = a.min_frame_errors
     if min_fe is None:
         min_fe = 5 if g.N > 50000 else 10 if g.N > 10000 else 20
     if a.codewords:
@@ -412,16 +479,16 @@ def _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, batch_fn, launch
             launcher = sim.AsyncLauncher(ctx, a.batch, run_launch)
         t0 = time.perf_counter()
         res = sim.simulate_point(run_batch, g.N, a.iterations, snr, a.batch, a.min_bit_errors, min_fe, a.max_frames,
-                                 device=device, launcher=launcher, first_round=a.first_round, iters_in_frames=True,
+                                 device=device, launcher=launcher, first_round=a.first_round, iters_in_frames=stops,
                                  resume=resume, on_round=on_round, on_round_interval=a.checkpoint_interval)
         dt = time.perf_counter() - t0
         c = res.counts
         ran = c["frames"] - (int(resume.acc[3]) if resume else 0)   # frames counted by this run
         return res, res.log_line(a.alist, extra), {
-            "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, "avg_iters": res.avg_iters, "seconds": dt,
-            "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None, "n_gpus": world,
+            "ebn0_db": snr, **c, "ber": res.ber, "fer": res.fer, **({"avg_iters": res.avg_iters} if stops else {}),
+            "seconds": dt, "mbit_s": ran * g.N / dt / 1e6 if dt > 0 else None, "n_gpus": world,
             "wilson95": sim.wilson_interval(c["frame_err"], c["frames"]), "precision": a.precision,
-            "gdbf": name, "kernel": info_fn(cfg)["kernel"], "rounds": res.rounds,
+            **family, "kernel": info_fn(cfg)["kernel"], "rounds": res.rounds,
             "frames_decoded": res.frames_decoded, "collectives": res.collectives}
 
     _run_points(a, ck, rank, g.N, run_point)

@@ -40,7 +40,8 @@ lines at the reference's constants and its R = 0.8413; *_wg forces the workgroup
 instance for the A/B of the two kernel shapes; where that is the library's own choice, the
 wavefront shape is measured with --lib on `make hwgdbfvariant VFLAGS=-DLDPC_HWGDBF_FORCE_WAVE`),
 src/newstat.cpp:305-429 (the rstat_* lines: 200 frames x 100 attempts as scripts/redecode_statistics_802.3.sh
-runs them; *_wg forces the workgroup-per-attempt kernel).
+runs them; *_wg forces the workgroup-per-attempt kernel). The fxms_* lines (fixed-point min-sum,
+fxms.hip) have no reference counterpart; nms_1944_* is the floating-point NMS beside them.
 """
 import argparse
 import csv
@@ -128,6 +129,19 @@ for _code, _tag, _snr in (("802_3_H.alist", "802_3", 4.0), ("PEGReg504x1008.alis
                 what=f"NGDBFhw on {_tag}, T<=600, {_prec} front end, "
                      f"{'hwgdbf_wg forced' if _k else 'the kernel the library chooses'}")
 
+# fixed-point min-sum (integer messages; no reference counterpart) on the headline workload: NMS 3/4, Ymax 31/16,
+# Q 5, T=50 at 1.5 dB, and at 3.0 dB with early stop; msg_bits 6 and 8 are one-byte messages, 12 two-byte ones.
+# The nms_1944_* lines are the floating-point NMS (alpha 1.25) beside them.
+for _snr, _es, _tag in ((1.5, False, ""), (3.0, True, "_es")):
+    for _bits in (6, 8, 12):
+        CONFIGS[f"fxms_1944_nms_m{_bits}{_tag}"] = dict(
+            kind="fxms", code="80211n_1944_r12.alist", prec="f32", T=50, batch=65536, snr=_snr, msg_bits=_bits,
+            early_stop=_es, what=f"fixed-point NMS 3/4 on 802.11n N=1944, msg_bits {_bits}, Q 5, T{'<=' if _es else '='}50")
+    for _prec in ("f32", "f64"):
+        CONFIGS[f"nms_1944_{_prec}{_tag}"] = dict(
+            kind="minsum", code="80211n_1944_r12.alist", variant="nms", prec=_prec, T=50, batch=65536, snr=_snr,
+            early_stop=_es, what=f"NMS alpha=1.25 on 802.11n N=1944, {_prec}, T{'<=' if _es else '='}50")
+
 # every attempt of every frame (src/newstat.cpp, src/replayGDBF.cpp): NF 200 frames x NR 100 attempts, the shape of
 # the reference's scripts/redecode_statistics_802.3.sh (802.3an at 4.0 dB, R 0.8125, T 1000, theta -0.525, noiseScale
 # 0.92, lambda 1, alpha 0.5, window 64) and N=1944 at 4.0 dB with the golden run's settings; `batch` counts frames
@@ -211,12 +225,19 @@ class Workload:
             self.launch_fn = self.ctx.hwgdbf_sim_launch
             info = self.ctx.hwgdbf_kernel_info(self.cfg)
             self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
+        elif c["kind"] == "fxms":
+            self.cfg = native.FxmsConfig(variant=native.NMS, T=c["T"], qbits=5, msg_bits=c["msg_bits"], nms_num=3,
+                                         nms_shift=2, early_stop=c["early_stop"], ymax=31 / 16, precision=prec)
+            self.launch_fn = self.ctx.fxms_sim_launch
+            info = self.ctx.fxms_kernel_info(self.cfg)
+            self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
         else:
             v = {"ms": dict(variant=native.MS), "nms": dict(variant=native.NMS, alpha=1.25),
                  "bp": dict(variant=native.BP),
                  "ddbmp": dict(variant=native.DDBMP, quantize=True, ymax=1.0, qbits=3)}[c["variant"]]
             sched = native.LAYERED if c.get("schedule") == "layered" else native.FLOODING
-            self.cfg = native.DecoderConfig(T=c["T"], precision=prec, schedule=sched, **v)
+            self.cfg = native.DecoderConfig(T=c["T"], precision=prec, schedule=sched, early_stop=c.get("early_stop", False),
+                                            **v)
             self.launch_fn = self.ctx.sim_launch
             self.kernel = self.ctx.kernel_info(self.cfg)["kernel"]
 
@@ -267,7 +288,7 @@ def timed(name, reps, lib):
         fr, _ = w.ctx.rgdbf_sim_batch(w.c["snr"], 0.5, w.cfg, seed=1, stream_id=0, first_cw=0, batch=w.c["batch"])
         ph = w.native.rgdbf_phases(fr["iters"], w.c["T"], w.c["maxphase"])
         out["phase_split"] = [int(x) for x in np.bincount(ph, minlength=w.c["maxphase"] + 1)[1:]]
-    if w.c["kind"] == "hwgdbf":
+    if w.c["kind"] in ("hwgdbf", "fxms"):
         out["lds_bytes_per_workgroup"] = w.lds_bytes
     m = lds_edges_cycles(w)
     if m:
