@@ -31,7 +31,8 @@
  *   - ldpc_fxms_decode_batch / ldpc_fxms_sim_* stand where ldpc_decode_batch /
  *     ldpc_sim_* do, for min-sum with integer messages of a chosen width (no
  *     reference program has them: its -D quantizeSamples quantises the samples
- *     only, src/decodeMinSum.cpp:480-489).
+ *     only, src/decodeMinSum.cpp:480-489). ldpc_fxlms_* are their row-layered
+ *     counterparts (a saturating posterior per bit, a message per edge).
  *   - ldpc_nb_* / ldpc_ems_* (ABI 5): non-binary GF(16) codes (BASELINE
  *     config 5). ldpc_nb_graph_create / _load_alist replace the NB-LDPC
  *     model's loadFile() (SystemC/NB-LDPC/src/alist.cpp:23-56,
@@ -184,7 +185,8 @@ void ldpc_graph_destroy(ldpc_graph *g);
 /* Row order and layer partition of the LAYERED schedule: row_order[M] lists
  * the rows in serial order, layer_ptr[nlayers+1] delimits the layers (runs
  * of rows that share no bit). Either array may be NULL (query nlayers
- * first). No reference counterpart. */
+ * first). Every graph has one (row degree up to 58; the floating-point LAYERED
+ * kernels take row degree up to 26). No reference counterpart. */
 int  ldpc_graph_layers(const ldpc_graph *g, int32_t *row_order, int32_t *layer_ptr, int *nlayers);
 
 /* ---- device context --------------------------------------------------- */
@@ -645,6 +647,70 @@ int  ldpc_fxms_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxm
 /* Kernel chosen for a cfg ("fxms_i8": one-byte messages, msg_bits <= 8; "fxms_i16")
  * and the LDS bytes of a workgroup. The cfg is checked first, also with a NULL context. */
 int  ldpc_fxms_kernel_info(ldpc_ctx *ctx, const ldpc_fxms_cfg *cfg, char *name, int name_len, int *lds_bytes);
+
+/* ---- layered fixed-point min-sum (fxlms) -------------------------------- */
+/* Row-layered MS / NMS / OMS in integers, as a hardware layered decoder computes it:
+ * a saturating posterior (APP) of app_bits per bit and a message of msg_bits per edge,
+ * updated in place row by row as Q = P - R_old, R_new = f(Q), P = Q + R_new. With
+ * Nq = 2^qbits, V = 2^(msg_bits - 1) - 1, A = 2^(app_bits - 1) - 1 and
+ * sgn(x) = x >= 0 ? +1 : -1:
+ *   front end  exactly ldpc_fxms_cfg's: the integer code Y in `precision`; the
+ *              uncoded decision is r = Y > 0 ? +1 : -1.
+ *   start      app_i = clamp(Y_i, -A, A); every c2v = 0.
+ *   iteration  for each check row j in the order ldpc_graph_layers() returns
+ *              (row_order), serially, with b_k the bit of its edge k:
+ *                x_k = clamp(app[b_k] - c2v[j][k], -V, V);
+ *                P = prod sgn(x_k), m1 <= m2 the two smallest |x_k| (m2 = V when the
+ *                row has one edge; a row of degree 0 does nothing);
+ *                mag = m2 at the position of the minimum, else m1; f as in fxms: MS as
+ *                is, NMS (mag * nms_num) >> nms_shift, OMS max(mag - beta, 0);
+ *                c_k = P sgn(x_k) f(mag); c2v[j][k] = c_k;
+ *                app[b_k] = clamp(x_k + c_k, -A, A), in int32 from the clamped x_k.
+ *   decision   d_i = app_i > 0 ? +1 : -1.
+ * T iterations (T = 0: d = r); early_stop as ldpc_fxms_cfg's: the result is D(s) for
+ * the smallest s in 0..T whose decisions have a zero syndrome (checked between whole
+ * iterations and after the last), s = T when there is none; frames[].iters = s and
+ * counts->iters += s; without it frames[].iters = 0 and counts->iters += T.
+ * Rows of one layer share no bit and integers commute exactly, so any parallel
+ * execution of a layer gives these results, and the result of a frame depends on the
+ * frame only. With app_bits = msg_bits + 1 and msg_bits >= qbits the APP clamp never
+ * acts (|x + c| <= 2 V < A); a decoder whose clamps never act reproduces the fp64
+ * LAYERED MS / OMS on grid samples bit for bit. A codeword's state -- N
+ * APPs (one byte each for app_bits <= 8, else two) and the packed messages of M rows
+ * (6 bytes a row, 8 with two-byte APPs, 4 more where a row has more than 26 edges) --
+ * lives in LDS: a graph where it exceeds 65536 bytes is LDPC_ERR_UNSUPPORTED (DVB-S2 is
+ * out of scope, as for fxms). No reference program computes this decoder. */
+typedef struct {
+    int32_t variant;     /* LDPC_MS | LDPC_NMS | LDPC_OMS; another ldpc_variant: LDPC_ERR_UNSUPPORTED */
+    int32_t precision;   /* front end only */
+    int32_t T;           /* >= 0 */
+    int32_t qbits;       /* 2..7  (|Y| <= 127) */
+    int32_t msg_bits;    /* 2..16 */
+    int32_t app_bits;    /* msg_bits..16 */
+    int32_t nms_num;     /* NMS: 1 <= nms_num <= 2^nms_shift */
+    int32_t nms_shift;   /* NMS: 0..7 */
+    int32_t beta;        /* OMS: >= 0 */
+    int32_t early_stop;  /* 0 | 1 */
+    double  ymax;        /* > 0 */
+} ldpc_fxlms_cfg;
+
+/* The five calls of fixed-point min-sum, argument for argument: given samples, the fused
+ * Monte-Carlo (the channel of frame f is the min-sum path's for the same (seed, stream_id,
+ * frame); the codeword table of ldpc_sim_set_codewords applies), its synchronous form, the
+ * form that also returns the samples drawn and their integer codes, and the kernel chosen
+ * ("fxlms_i8": one-byte APPs and messages, app_bits <= 8; "fxlms_i16") with the LDS bytes
+ * of a workgroup. The cfg is checked first, also with a NULL context. */
+int  ldpc_fxlms_decode_batch(ldpc_ctx *ctx, const void *y, int batch, const ldpc_fxlms_cfg *cfg, const int8_t *c,
+                             int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts);
+int  ldpc_fxlms_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev);
+int  ldpc_fxlms_sim_batch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames,
+                          ldpc_counts *accum);
+int  ldpc_fxlms_sim_trace(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out,
+                          int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *accum);
+int  ldpc_fxlms_kernel_info(ldpc_ctx *ctx, const ldpc_fxlms_cfg *cfg, char *name, int name_len, int *lds_bytes);
 
 /* ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ------ */
 /* Messages are reliabilities over GF(q) (0 = most likely symbol); check

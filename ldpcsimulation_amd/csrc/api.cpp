@@ -11,6 +11,7 @@
 #include "rstat.h"
 #include "hwgdbf.h"
 #include "fxms.h"
+#include "fxlms.h"
 #include "bp.h"
 #include "ddbmp.h"
 #include "nb.h"
@@ -47,7 +48,7 @@ static const char *check_site_name(unsigned s)
         "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
         "hwgdbf noise sample", "rstat decision byte", "rstat check parity", "rows_es gather (app entry)",
         "rows_es scatter (c2v slot)", "rows_es bit read (c2v slot)", "rows_es app write", "fxms message slot",
-        "fxms decision byte"};
+        "fxms decision byte", "fxlms schedule entry", "fxlms APP", "fxlms row state"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -57,7 +58,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
                                               check_take_rgdbf, check_take_hwgdbf, check_take_rstat, check_take_rows_es,
-                                              check_take_fxms};
+                                              check_take_fxms, check_take_fxlms};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -79,6 +80,9 @@ struct ldpc_ctx : CtxCore {
     DevBuf rs_att_stage, rs_unc, rs_tr_stage[4];          // every-attempt decoders: attempt results, uncoded errors, traces
     DevBuf hw_ptr_stage, hw_it_stage;                     // NGDBFhw: start pointers in, iterations run out
     DevBuf fx_code_stage;                                 // fixed-point min-sum: the integer codes out
+    bool has_fxl = false;                                 // layered fixed-point min-sum: the layered row order, built by its first launch
+    ldpc::FxlmsSched fxl{};
+    DevBuf fxl_sched;
     int cw_rows = 0;
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
     bool has_rs = false;
@@ -207,6 +211,27 @@ static hipError_t upload_layer_sched(const ldpc::LayerSchedule &lh, DevBuf &buf,
     return hipSuccess;
 }
 
+// The layered row order as fxlms.hip reads it: row n is the check at layered position n.
+static hipError_t upload_fxlms_sched(const ldpc_graph &g, const ldpc::LayerSchedule &lh, DevBuf &buf, ldpc::FxlmsSched &sc)
+{
+    const int M = g.M, dcs = g.maxdc > 0 ? g.maxdc : 1;
+    std::vector<int32_t> cols((size_t)dcs * M, 0);
+    std::vector<uint8_t> deg(M, 0);
+    for (int n = 0; n < M; ++n) {
+        const int j = lh.row_order[n], d = g.row_deg[j];
+        deg[n] = (uint8_t)d;
+        for (int k = 0; k < dcs; ++k)   // edges past the row repeat its last bit
+            cols[(size_t)k * M + n] = d ? g.row_cols[(size_t)j * dcs + std::min(k, d - 1)] : 0;
+    }
+    Blob b(256);
+    const size_t o_lp = b.add(lh.lptr), o_c = b.add(cols), o_d = b.add(deg);
+    const hipError_t e = upload(b, buf);
+    if (e != hipSuccess) return e;
+    sc = {g.N, M, dcs, (int)lh.lptr.size() - 1, section<int32_t>(buf, o_lp), section<int32_t>(buf, o_c),
+          section<uint8_t>(buf, o_d)};
+    return hipSuccess;
+}
+
 // ----------------------------------------------------------------- the binary families' shared steps
 static const char kFramesDev[] = "frames_dev must be a device pointer";
 
@@ -259,6 +284,48 @@ template <class Args, class Cfg> static void redecode_fill(Args &a, ldpc_ctx *c,
     a.w = cfg->alpha * cfg->ymax;
     a.ymax = cfg->ymax;
     a.qmax = 1.0;
+    fill_accounting(a, *c);
+}
+
+// The rules of the fields ldpc_fxms_cfg and ldpc_fxlms_cfg share; own() holds the cfg's own
+// rule that comes after the precision's (fxms: reserved).
+template <class Cfg, class Own> static int fx_check_cfg(const Cfg *cfg, Own own)
+{
+    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
+    if (cfg->variant != LDPC_MS && cfg->variant != LDPC_NMS && cfg->variant != LDPC_OMS)
+        return set_err(cfg->variant == LDPC_BP || cfg->variant == LDPC_DDBMP ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_INVALID,
+                       "variant %d: fixed-point min-sum is MS, NMS or OMS", cfg->variant);
+    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
+        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
+    RC_TRY(own());
+    if (cfg->T < 0) return set_err(LDPC_ERR_INVALID, "T must be >= 0");
+    if (cfg->qbits < 2 || cfg->qbits > 7) return set_err(LDPC_ERR_INVALID, "qbits must be in 2..7");
+    if (cfg->msg_bits < 2 || cfg->msg_bits > 16) return set_err(LDPC_ERR_INVALID, "msg_bits must be in 2..16");
+    if (cfg->variant == LDPC_NMS) {
+        if (cfg->nms_shift < 0 || cfg->nms_shift > 7) return set_err(LDPC_ERR_INVALID, "nms_shift must be in 0..7");
+        if (cfg->nms_num < 1 || cfg->nms_num > (1 << cfg->nms_shift))
+            return set_err(LDPC_ERR_INVALID, "nms_num must be in 1..2^nms_shift = %d", 1 << cfg->nms_shift);
+    }
+    if (cfg->variant == LDPC_OMS && cfg->beta < 0) return set_err(LDPC_ERR_INVALID, "beta must be >= 0");
+    if (cfg->early_stop != 0 && cfg->early_stop != 1) return set_err(LDPC_ERR_INVALID, "early_stop must be 0 or 1");
+    if (!(cfg->ymax > 0) || !std::isfinite(cfg->ymax)) return set_err(LDPC_ERR_INVALID, "ymax must be > 0");
+    return LDPC_OK;
+}
+
+// The launch arguments both fixed-point min-sum cfgs set.
+template <class Args, class Cfg> static void fx_fill(Args &a, ldpc_ctx *c, const Cfg *cfg, int batch)
+{
+    std::memset((void *)&a, 0, sizeof a);
+    a.batch = batch;
+    a.T = cfg->T;
+    a.variant = cfg->variant;   // LDPC_MS / NMS / OMS are V_MS / V_NMS / V_OMS
+    a.nq1 = (1 << cfg->qbits) - 1;
+    a.vmax = (1 << (cfg->msg_bits - 1)) - 1;
+    a.nms_num = cfg->nms_num;
+    a.nms_shift = cfg->nms_shift;
+    a.beta = cfg->beta;
+    a.early_stop = cfg->early_stop;
+    a.ymax = cfg->ymax;
     fill_accounting(a, *c);
 }
 
@@ -333,7 +400,7 @@ int ldpc_graph_layers(const ldpc_graph *g, int32_t *row_order, int32_t *layer_pt
     ldpc::LayerSchedule lh;
     std::string err;
     try {
-        err = ldpc::build_flood_schedule(*g, fh);
+        err = ldpc::build_flood_schedule(*g, fh, ldpc::kMaxRowDegree);   // the order alone: every row degree
         if (err.empty()) err = ldpc::build_layers(*g, fh, lh);
     } catch (const std::bad_alloc &) {
         return set_err(LDPC_ERR_NOMEM, "layer schedule out of memory");
@@ -406,7 +473,7 @@ static void ctx_free(ldpc_ctx *c)
     if (!c) return;
     c->destroy({&c->graph, &c->hist, &c->y_stage, &c->c_stage, &c->d_stage, &c->fw_stage, &c->cw_table, &c->gscratch,
                 &c->sched, &c->sched_pp, &c->sched_ppi, &c->divcheck, &c->fsched, &c->lsched, &c->p_stage, &c->redo,
-                &c->hw_ptr_stage, &c->hw_it_stage, &c->fx_code_stage, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
+                &c->hw_ptr_stage, &c->hw_it_stage, &c->fx_code_stage, &c->fxl_sched, &c->rs_att_stage, &c->rs_unc, &c->rs_tr_stage[0], &c->rs_tr_stage[1],
                 &c->rs_tr_stage[2], &c->rs_tr_stage[3]});
     if (c->aux.fork) (void)hipEventDestroy(c->aux.fork);
     if (c->aux.join) (void)hipEventDestroy(c->aux.join);
@@ -1489,25 +1556,7 @@ int ldpc_hwgdbf_kernel_info(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, char *name,
 // ----------------------------------------------------------------- fixed-point min-sum
 static int fxms_check_cfg(const ldpc_fxms_cfg *cfg)
 {
-    if (!cfg) return set_err(LDPC_ERR_INVALID, "cfg is null");
-    if (cfg->variant != LDPC_MS && cfg->variant != LDPC_NMS && cfg->variant != LDPC_OMS)
-        return set_err(cfg->variant == LDPC_BP || cfg->variant == LDPC_DDBMP ? LDPC_ERR_UNSUPPORTED : LDPC_ERR_INVALID,
-                       "variant %d: fixed-point min-sum is MS, NMS or OMS", cfg->variant);
-    if (cfg->precision != LDPC_F32 && cfg->precision != LDPC_F64)
-        return set_err(LDPC_ERR_INVALID, "bad precision %d", cfg->precision);
-    if (cfg->reserved != 0) return set_err(LDPC_ERR_INVALID, "reserved must be 0");
-    if (cfg->T < 0) return set_err(LDPC_ERR_INVALID, "T must be >= 0");
-    if (cfg->qbits < 2 || cfg->qbits > 7) return set_err(LDPC_ERR_INVALID, "qbits must be in 2..7");
-    if (cfg->msg_bits < 2 || cfg->msg_bits > 16) return set_err(LDPC_ERR_INVALID, "msg_bits must be in 2..16");
-    if (cfg->variant == LDPC_NMS) {
-        if (cfg->nms_shift < 0 || cfg->nms_shift > 7) return set_err(LDPC_ERR_INVALID, "nms_shift must be in 0..7");
-        if (cfg->nms_num < 1 || cfg->nms_num > (1 << cfg->nms_shift))
-            return set_err(LDPC_ERR_INVALID, "nms_num must be in 1..2^nms_shift = %d", 1 << cfg->nms_shift);
-    }
-    if (cfg->variant == LDPC_OMS && cfg->beta < 0) return set_err(LDPC_ERR_INVALID, "beta must be >= 0");
-    if (cfg->early_stop != 0 && cfg->early_stop != 1) return set_err(LDPC_ERR_INVALID, "early_stop must be 0 or 1");
-    if (!(cfg->ymax > 0) || !std::isfinite(cfg->ymax)) return set_err(LDPC_ERR_INVALID, "ymax must be > 0");
-    return LDPC_OK;
+    return fx_check_cfg(cfg, [&] { return cfg->reserved != 0 ? set_err(LDPC_ERR_INVALID, "reserved must be 0") : LDPC_OK; });
 }
 
 // The kernel instance for cfg->msg_bits on the context's graph, or the refusal when one codeword's state exceeds LDS.
@@ -1525,18 +1574,7 @@ static int fxms_pick(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, ldpc::FxmsChoice &ch
 // Host work only (its refusals come before enter()).
 static int fxms_fill(ldpc::FxmsArgs &a, ldpc::FxmsChoice &ch, ldpc_ctx *c, const ldpc_fxms_cfg *cfg, int batch)
 {
-    std::memset((void *)&a, 0, sizeof a);
-    a.batch = batch;
-    a.T = cfg->T;
-    a.variant = cfg->variant;   // LDPC_MS / NMS / OMS are V_MS / V_NMS / V_OMS
-    a.nq1 = (1 << cfg->qbits) - 1;
-    a.vmax = (1 << (cfg->msg_bits - 1)) - 1;
-    a.nms_num = cfg->nms_num;
-    a.nms_shift = cfg->nms_shift;
-    a.beta = cfg->beta;
-    a.early_stop = cfg->early_stop;
-    a.ymax = cfg->ymax;
-    fill_accounting(a, *c);
+    fx_fill(a, c, cfg, batch);
     return fxms_pick(c, cfg, ch);
 }
 
@@ -1619,6 +1657,144 @@ int ldpc_fxms_kernel_info(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, char *name, int
     if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
     ldpc::FxmsChoice ch;
     RC_TRY(fxms_pick(c, cfg, ch));
+    return report_choice(ch, name, name_len, lds_bytes);
+}
+
+// ----------------------------------------------------------------- layered fixed-point min-sum
+static int fxlms_check_cfg(const ldpc_fxlms_cfg *cfg)
+{
+    RC_TRY(fx_check_cfg(cfg, [] { return LDPC_OK; }));
+    if (cfg->app_bits < cfg->msg_bits || cfg->app_bits > 16)
+        return set_err(LDPC_ERR_INVALID, "app_bits must be in msg_bits..16 = %d..16", cfg->msg_bits);
+    return LDPC_OK;
+}
+
+// The kernel instance for cfg->app_bits on the context's graph, or the refusal when one codeword's state exceeds LDS.
+// (The choice reads the graph's sizes only: no schedule, no device.)
+static int fxlms_pick(ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, ldpc::FxlmsChoice &ch)
+{
+    ldpc::FxlmsSched sizes;
+    sizes.N = c->g->N;
+    sizes.M = c->g->M;
+    sizes.dcs = c->g->maxdc > 0 ? c->g->maxdc : 1;
+    ch = ldpc::fxlms_choose(sizes, cfg->app_bits);
+    if (!ch.name[0])
+        return set_err(LDPC_ERR_UNSUPPORTED,
+                       "layered fixed-point min-sum keeps a codeword in LDS: N APPs + the packed state of M rows = %d "
+                       "bytes exceed the bound of %d",
+                       ch.cw_bytes, ldpc::kFxlmsMaxLds);
+    return LDPC_OK;
+}
+
+// Host work only (its refusals come before enter()).
+static int fxlms_fill(ldpc::FxlmsArgs &a, ldpc::FxlmsChoice &ch, ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, int batch)
+{
+    fx_fill(a, c, cfg, batch);
+    a.amax = (1 << (cfg->app_bits - 1)) - 1;
+    return fxlms_pick(c, cfg, ch);
+}
+
+// The layered row order on the device, built and uploaded by the context's first fxlms launch (after
+// enter()), so that a context that never decodes with fxlms is created as before.
+static int fxlms_sched(ldpc_ctx *c)
+{
+    if (c->has_fxl) return LDPC_OK;
+    ldpc::FloodSchedule fh;
+    ldpc::LayerSchedule lh;
+    std::string err;
+    try {
+        err = ldpc::build_flood_schedule(*c->g, fh, ldpc::kMaxRowDegree);
+        if (err.empty()) err = ldpc::build_layers(*c->g, fh, lh);
+    } catch (const std::bad_alloc &) {
+        return set_err(LDPC_ERR_NOMEM, "layer schedule out of memory");
+    }
+    if (!err.empty()) return set_err(LDPC_ERR_UNSUPPORTED, "no layer schedule for this graph: %s", err.c_str());
+    HIP_TRY(upload_fxlms_sched(*c->g, lh, c->fxl_sched, c->fxl));
+    c->has_fxl = true;
+    return LDPC_OK;
+}
+
+static int fxlms_run(ldpc_ctx *c, const ldpc::FxlmsArgs &a, const ldpc::FxlmsChoice &ch, bool f64)
+{
+    RC_TRY(fxlms_sched(c));
+    RC_TRY(c->begin_launch());
+    HIP_TRY(ldpc::fxlms_launch(c->fxl, a, f64, ch, c->num_cus, c->stream));
+    return c->end_launch();
+}
+
+int ldpc_fxlms_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_fxlms_cfg *cfg, const int8_t *cw,
+                            int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+{
+    if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
+    RC_TRY(fxlms_check_cfg(cfg));
+    RC_TRY(check_batch(*c, batch));
+    ldpc::FxlmsArgs a;
+    ldpc::FxlmsChoice ch;
+    RC_TRY(fxlms_fill(a, ch, c, cfg, batch));
+    RC_TRY(c->enter());
+    const bool f64 = cfg->precision == LDPC_F64;
+    SyncCall s(*c);
+    RC_TRY(stage_given(s, c, a, f64, y, nullptr, 0, nullptr, cw));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(s.snapshot());
+    RC_TRY(fxlms_run(c, a, ch, f64));
+    return s.finish(counts);
+}
+
+// The refusals of the ldpc_fxlms_sim_* calls that need no device, and the launch arguments of cfg.
+static int fxlms_sim_setup(ldpc_ctx *c, const SimCall &q, const ldpc_fxlms_cfg *cfg, ldpc::FxlmsArgs &a,
+                           ldpc::FxlmsChoice &ch)
+{
+    RC_TRY(check_sim(c, [&] { return fxlms_check_cfg(cfg); }, q, false));
+    RC_TRY(fxlms_fill(a, ch, c, cfg, q.batch));
+    fill_sim(a, *c, q);
+    fill_cw_table(a, *c);
+    return LDPC_OK;
+}
+
+int ldpc_fxlms_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    ldpc::FxlmsArgs a;
+    ldpc::FxlmsChoice ch;
+    RC_TRY(fxlms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    RC_TRY(require_device(frames_dev, kFramesDev));
+    RC_TRY(c->enter());
+    a.frame_res = (int4 *)frames_dev;
+    return fxlms_run(c, a, ch, cfg->precision == LDPC_F64);
+}
+
+int ldpc_fxlms_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out, int8_t *d_out,
+                         ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    ldpc::FxlmsArgs a;
+    ldpc::FxlmsChoice ch;
+    RC_TRY(fxlms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    RC_TRY(c->enter());
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    const size_t nb = (size_t)batch * c->g->N;
+    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), a.y_out));
+    RC_TRY(s.out(ycode_out, c->fx_code_stage, nb, a.ycode_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(fxlms_run(c, a, ch, cfg->precision == LDPC_F64));
+    return s.finish(accum);
+}
+
+int ldpc_fxlms_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    return ldpc_fxlms_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames,
+                                accum);
+}
+
+int ldpc_fxlms_kernel_info(ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, char *name, int name_len, int *lds_bytes)
+{
+    RC_TRY(fxlms_check_cfg(cfg));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    ldpc::FxlmsChoice ch;
+    RC_TRY(fxlms_pick(c, cfg, ch));
     return report_choice(ch, name, name_len, lds_bytes);
 }
 

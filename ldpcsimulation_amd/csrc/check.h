@@ -51,6 +51,9 @@ enum CheckSite : unsigned {
     CHK_ES_APP_WRITE,      // rows_es: app entry a bit slot writes          (< N + 2)
     CHK_FXMS_SLOT,         // fxms: message slot of a check / bit edge      (< maxdc * M)
     CHK_FXMS_BIT,          // fxms: decision byte a check gathers           (< N)
+    CHK_FXLMS_SCHED,       // fxlms: schedule entry of a row's edge         (< maxdc * M)
+    CHK_FXLMS_BIT,         // fxlms: APP a row gathers / scatters           (< N)
+    CHK_FXLMS_ROW,         // fxlms: packed state of a layer's row          (< M)
     CHK_SITES
 };
 
@@ -117,6 +120,7 @@ hipError_t check_take_hwgdbf(CheckRec *out);
 hipError_t check_take_rstat(CheckRec *out);
 hipError_t check_take_rows_es(CheckRec *out);
 hipError_t check_take_fxms(CheckRec *out);
+hipError_t check_take_fxlms(CheckRec *out);
 #endif
 
 }  // namespace ldpc

@@ -1,0 +1,40 @@
+// fxlms.h -- internal launch interface of the layered fixed-point min-sum kernel (fxlms.hip):
+// row-layered MS / NMS / OMS with a saturating app_bits-wide posterior per bit and a
+// msg_bits-wide message per edge (include/ldpc_hip.h ldpc_fxlms_cfg has the
+// definition; no reference program computes this, its anchor is the fp64 layered decoder on
+// samples that sit on the quantiser grid).
+#pragma once
+#include "fxms.h"
+
+namespace ldpc {
+
+// The fixed-point min-sum arguments (front end, check-node rule, accounting) and the APP clamp.
+struct FxlmsArgs : FxmsArgs {
+    int amax;                       // A = 2^(app_bits - 1) - 1
+};
+
+// Device copy of the layered row order the kernel walks (graph.h LayerSchedule: the order of
+// ldpc_graph_layers), as the kernel reads it: row n is the check at layered position n.
+struct FxlmsSched {
+    int N = 0, M = 0, dcs = 0, nlayers = 0;
+    const int32_t *lptr = nullptr;  // [nlayers + 1] layered positions of each layer
+    const int32_t *cols = nullptr;  // [dcs * M] slot-major: bit of edge k of row n at k * M + n (pads: the row's last bit)
+    const uint8_t *deg = nullptr;   // [M]
+};
+
+struct FxlmsChoice {
+    const char *name = "";          // "fxlms_i8" | "fxlms_i16"; empty: the state does not fit
+    int lds_bytes = 0;              // dynamic LDS of a workgroup
+    int cw_bytes = 0;               // state bytes of one codeword
+    int threads = 0, cw_per_block = 0;
+    bool wide = false;              // int16 APPs, 15-bit magnitudes (app_bits > 8)
+    bool staged = false;            // the schedule sits in LDS beside the codewords (lds_bytes includes it)
+};
+
+constexpr int kFxlmsMaxLds = 64 * 1024;   // one codeword's state must fit (the fxms bound)
+
+FxlmsChoice fxlms_choose(const FxlmsSched &sc, int app_bits);
+hipError_t fxlms_launch(const FxlmsSched &sc, const FxlmsArgs &a, bool f64, const FxlmsChoice &ch, int num_cus,
+                        hipStream_t s);
+
+}  // namespace ldpc

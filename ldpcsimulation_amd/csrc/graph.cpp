@@ -414,11 +414,12 @@ static std::vector<int> chain_order(int n, const std::vector<int> &next)
     return order;
 }
 
-std::string build_flood_schedule(const ldpc_graph &g, FloodSchedule &s)
+std::string build_flood_schedule(const ldpc_graph &g, FloodSchedule &s, int max_dc)
 {
     s = FloodSchedule();
     const int N = g.N, M = g.M, dcs = std::max(g.maxdc, 1);
-    if (g.maxdc > 26) return "row degree exceeds the flood kernel's packed row state";
+    if (g.maxdc > max_dc)
+        return max_dc == 26 ? "row degree exceeds the flood kernel's packed row state" : "row degree exceeds the row order's bound";
     s.dc = std::max(g.maxdc, 1);
     // rows of each bit
     auto rows_of = [&](int c, int e) { return (int)(g.col_refs[g.col_ptr[c] + e] >> kRefShift); };

@@ -74,7 +74,10 @@ struct FloodSchedule {
     std::vector<int32_t> gbase;       // [ngroups]: edge e (nlist order) of position p at gbase[p/64] + 64e + p%64
     double coalesced = 0;             // diagnostic: share of slot accesses whose lane neighbour is +1
 };
-std::string build_flood_schedule(const ldpc_graph &g, FloodSchedule &s);
+// max_dc: the largest row degree taken. 26 is the flood and layered kernels' packed row state
+// (kernels.h kPackedMaxDc); the row order alone (ldpc_graph_layers, fxlms.hip) is built up to
+// kMaxRowDegree.
+std::string build_flood_schedule(const ldpc_graph &g, FloodSchedule &s, int max_dc = 26);
 
 // Layered schedule (layered.hip, k_decode_layered_*): rows grouped into
 // layers of rows that share no bit, by first-fit colouring of whole row

@@ -247,6 +247,38 @@ class FxmsConfig:
                         self.beta, int(self.early_stop), 0, self.ymax)
 
 
+class _FxlmsCfg(C.Structure):
+    _fields_ = [("variant", C.c_int32), ("precision", C.c_int32), ("T", C.c_int32), ("qbits", C.c_int32),
+                ("msg_bits", C.c_int32), ("app_bits", C.c_int32), ("nms_num", C.c_int32), ("nms_shift", C.c_int32),
+                ("beta", C.c_int32), ("early_stop", C.c_int32), ("ymax", C.c_double)]
+
+
+@dataclass
+class FxlmsConfig:
+    """Layered fixed-point min-sum (include/ldpc_hip.h ldpc_fxlms_cfg): FxmsConfig's fields and the
+    width of the saturating posteriors, app_bits (None: msg_bits + 1, at most 16, where the APP
+    clamp never acts for msg_bits >= qbits)."""
+    variant: int = MS
+    T: int = 10
+    qbits: int = 5
+    msg_bits: int = 6
+    app_bits: Optional[int] = None
+    nms_num: int = 3
+    nms_shift: int = 2
+    beta: int = 1
+    early_stop: bool = False
+    ymax: float = 31 / 16
+    precision: int = F64
+
+    def __post_init__(self):
+        if self.app_bits is None:
+            self.app_bits = min(self.msg_bits + 1, 16)
+
+    def _c(self) -> _FxlmsCfg:
+        return _FxlmsCfg(self.variant, self.precision, self.T, self.qbits, self.msg_bits, self.app_bits, self.nms_num,
+                         self.nms_shift, self.beta, int(self.early_stop), self.ymax)
+
+
 def rgdbf_phases(iters, T: int, maxphase: int):
     """Phases a frame ran, from its total iterations (int or array): a failed phase runs
     exactly T iterations and a satisfied one fewer, so phases = min(maxphase, iters // T + 1)."""
@@ -385,6 +417,11 @@ _SIG = {
     "ldpc_fxms_sim_batch": (_sim(_FxmsCfg, _vp, C.POINTER(Counts)), _i32),
     "ldpc_fxms_sim_trace": (_sim(_FxmsCfg, _vp, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
     "ldpc_fxms_kernel_info": (_info(_FxmsCfg), _i32),
+    "ldpc_fxlms_decode_batch": ([_vp, _vp, _i32, C.POINTER(_FxlmsCfg), _vp, _vp, _vp, C.POINTER(Counts)], _i32),
+    "ldpc_fxlms_sim_launch": (_sim(_FxlmsCfg, _vp), _i32),
+    "ldpc_fxlms_sim_batch": (_sim(_FxlmsCfg, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_fxlms_sim_trace": (_sim(_FxlmsCfg, _vp, _vp, _vp, _vp, C.POINTER(Counts)), _i32),
+    "ldpc_fxlms_kernel_info": (_info(_FxlmsCfg), _i32),
     "ldpc_nb_graph_create": ([_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)], _i32),
     "ldpc_nb_graph_load_alist": ([C.c_char_p, C.POINTER(_vp)], _i32),
     "ldpc_nb_graph_info": ([_vp] + [_pi32] * 6, _i32),
@@ -407,7 +444,9 @@ _lib = None
 
 # exports added without an ABI bump: the product library has them, an older A/B build may not
 _ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_redo_list", "ldpc_ctx_pp_row_slots", "ldpc_fxms_decode_batch",
-                 "ldpc_fxms_sim_launch", "ldpc_fxms_sim_batch", "ldpc_fxms_sim_trace", "ldpc_fxms_kernel_info"}
+                 "ldpc_fxms_sim_launch", "ldpc_fxms_sim_batch", "ldpc_fxms_sim_trace", "ldpc_fxms_kernel_info",
+                 "ldpc_fxlms_decode_batch", "ldpc_fxlms_sim_launch", "ldpc_fxlms_sim_batch", "ldpc_fxlms_sim_trace",
+                 "ldpc_fxlms_kernel_info"}
 
 
 def lib():
@@ -895,6 +934,37 @@ class Context:
 
     def fxms_kernel_info(self, cfg: FxmsConfig) -> dict:
         return _kernel_info(lib().ldpc_fxms_kernel_info, self._h, C.byref(cfg._c()))
+
+    # ---- layered fixed-point min-sum (saturating posteriors, integer messages) ----
+    def fxlms_decode(self, y, cfg: FxlmsConfig, c=None, want_decisions: bool = True):
+        """Decode raw channel samples y[batch, N] in the order of Graph.layers(). Returns (d, frames,
+        Counts); frames' iters are 0, or with early_stop the iteration whose decisions are returned."""
+        y, batch, c, _ = _given(self.graph.N, cfg, y, c)
+        return self._decode(lib().ldpc_fxlms_decode_batch, y, cfg, c, want_decisions)
+
+    def fxlms_sim_launch(self, ebn0_db: float, R: float, cfg: FxlmsConfig, seed: int, stream_id: int, first_cw: int,
+                         batch: int, frames_dev=None):
+        _sim_launch(lib().ldpc_fxlms_sim_launch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, frames_dev)
+
+    def fxlms_sim_batch(self, ebn0_db: float, R: float, cfg: FxlmsConfig, seed: int, stream_id: int, first_cw: int,
+                        batch: int, want_frames: bool = True):
+        return _sim_batch(lib().ldpc_fxlms_sim_batch, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                          want_frames=want_frames)
+
+    def fxlms_sim_trace(self, ebn0_db: float, R: float, cfg: FxlmsConfig, seed: int, stream_id: int, first_cw: int,
+                        batch: int):
+        """fxlms_sim_batch that also returns the samples drawn and their integer codes:
+        (y, ycode, d, frames, Counts)."""
+        N = self.graph.N
+        y = np.empty((batch, N), dtype=np.float64 if cfg.precision == F64 else np.float32)
+        code = np.empty((batch, N), dtype=np.int8)
+        d = np.empty((batch, N), dtype=np.int8)
+        fr, cnt = _sim_batch(lib().ldpc_fxlms_sim_trace, self._h, ebn0_db, R, cfg, seed, stream_id, first_cw, batch,
+                             y, code, d)
+        return y, code, d, fr, cnt
+
+    def fxlms_kernel_info(self, cfg: FxlmsConfig) -> dict:
+        return _kernel_info(lib().ldpc_fxlms_kernel_info, self._h, C.byref(cfg._c()))
 
 
 # ---- non-binary GF(q) codes, Extended Min-Sum (BASELINE config 5) ----

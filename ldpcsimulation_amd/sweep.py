@@ -32,7 +32,10 @@ line for each point.
     # fixed-point min-sum: integer messages of --msg-bits bits, NMS as (m * NUM) >> SHIFT, OMS as max(m - B, 0)
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 50 --fxms --variant nms --scale 3 2 \\
         --quantize 1.9375 5 --msg-bits 6 --early-stop
-Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (--fxms: SNR BER avgIt FER T Ymax Q msgBits [num shift] [beta] alist; DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
+    # its row-layered form: saturating posteriors of --app-bits bits (default msg-bits + 1), rows in the graph's layer order
+    python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 25 --fxlms --variant nms --scale 3 2 \\
+        --quantize 1.9375 5 --msg-bits 8 --app-bits 9 --early-stop
+Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (--fxms: SNR BER avgIt FER T Ymax Q msgBits [num shift] [beta] alist; --fxlms: SNR BER avgIt FER T Ymax Q msgBits appBits [num shift] [beta] alist; DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
 BER over coded bits, 4 per GF(16) symbol; --gdbf: SNR BER avgIt FER T theta noiseScale lambda alpha windowsize Ymax
 [maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job;
 --hwgdbf: SNR BER avgIt FER T theta0 noiseScale w Ymax NQ maxphase qlen alist).
@@ -107,7 +110,11 @@ def parse(argv=None):
     p.add_argument("--fxms", action="store_true",
                    help="fixed-point min-sum (integer messages): --variant ms|nms|oms, --quantize YMAX Q (default 1.9375 5), "
                         "-T, --precision (of the front end) and --early-stop are reused")
-    p.add_argument("--msg-bits", type=int, help="--fxms: message width in bits, 2..16 (default 6)")
+    p.add_argument("--fxlms", action="store_true",
+                   help="layered fixed-point min-sum (saturating posteriors, integer messages, the graph's layer order): "
+                        "the settings of --fxms and --app-bits")
+    p.add_argument("--app-bits", type=int, help="--fxlms: posterior width in bits, msg-bits..16 (default msg-bits + 1)")
+    p.add_argument("--msg-bits", type=int, help="--fxms / --fxlms: message width in bits, 2..16 (default 6)")
     p.add_argument("--scale", type=int, nargs=2, metavar=("NUM", "SHIFT"),
                    help="--fxms --variant nms: magnitudes become (m * NUM) >> SHIFT (default 3 2)")
     p.add_argument("--beta", type=int, help="--fxms --variant oms: magnitudes become max(m - B, 0) (default 1)")
@@ -139,19 +146,24 @@ def parse(argv=None):
     a = p.parse_args(argv)
     if a.early_stop and a.schedule == "layered":
         p.error("--early-stop is not supported with --schedule layered")
-    if a.fxms:
+    if a.fxms and a.fxlms:
+        p.error("--fxms and --fxlms exclude each other")
+    if a.fxms or a.fxlms:
+        fx = "--fxlms" if a.fxlms else "--fxms"
         if a.gdbf or a.hwgdbf or a.ems or a.schedule != "flooding":
-            p.error("--fxms excludes --gdbf, --hwgdbf, --ems and --schedule layered")
+            p.error(fx + " excludes --gdbf, --hwgdbf, --ems and --schedule layered")
         if a.variant not in ("ms", "nms", "oms"):
-            p.error("--fxms is --variant ms, nms or oms")
+            p.error(fx + " is --variant ms, nms or oms")
         if a.saturate is not None or a.ymax is not None or a.qbits is not None or a.alpha != 1.0 or a.delta != 0.0:
-            p.error("--fxms takes its settings from --quantize YMAX Q, --msg-bits, --scale NUM SHIFT and --beta")
+            p.error(fx + " takes its settings from --quantize YMAX Q, --msg-bits, --scale NUM SHIFT and --beta")
         if (a.scale is not None and a.variant != "nms") or (a.beta is not None and a.variant != "oms"):
-            p.error("--fxms: --scale belongs to --variant nms and --beta to --variant oms")
+            p.error(fx + ": --scale belongs to --variant nms and --beta to --variant oms")
     else:
         for n in ("msg_bits", "scale", "beta"):
             if getattr(a, n) is not None:
-                p.error("--" + n.replace("_", "-") + " belongs to --fxms")
+                p.error("--" + n.replace("_", "-") + " belongs to --fxms / --fxlms")
+    if a.app_bits is not None and not a.fxlms:
+        p.error("--app-bits belongs to --fxlms")
     gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
     if a.hwgdbf:
         if a.gdbf or a.ems or a.schedule != "flooding" or a.variant != "ms":
@@ -197,6 +209,8 @@ def _checkpoint_config(a) -> dict:
         ddbmp = {"hwgdbf": True, **_hwgdbf_settings(a)}
     if getattr(a, "fxms", False):   # likewise: every field of the cfg, so another width is another sweep
         ddbmp = {"fxms": True, **_fxms_settings(a)}
+    if getattr(a, "fxlms", False):   # likewise: the fxms keys, the switch and the posterior width
+        ddbmp = {"fxms": False, "fxlms": True, **_fxlms_settings(a)}
     if _min_sum_early_stop(a):   # likewise (the "early_stop" key below is the EMS setting)
         ddbmp = {**ddbmp, "min_sum_early_stop": True}
     return {**ddbmp, "alist": os.path.basename(a.alist), "alist_md5": checkpoint.file_digest(a.alist), "rate": a.rate,
@@ -239,6 +253,13 @@ def _fxms_settings(a) -> dict:
         s["nms_num"], s["nms_shift"] = a.scale
     if a.beta is not None:
         s["beta"] = a.beta
+    return s
+
+
+def _fxlms_settings(a) -> dict:
+    """The --fxlms settings with their defaults filled in: --fxms's and app_bits."""
+    s = _fxms_settings(a)
+    s["app_bits"] = a.app_bits if a.app_bits is not None else min(s["msg_bits"] + 1, 16)
     return s
 
 
@@ -305,7 +326,7 @@ def main(argv=None) -> int:
         return _ems_sweep(a, seed, world, rank, device, ck)
     if a.gdbf or a.hwgdbf:
         return _gdbf_sweep(a, seed, world, rank, device, ck)
-    if a.fxms:
+    if a.fxms or a.fxlms:
         return _fxms_sweep(a, seed, world, rank, device, ck)
     cfg = native.DecoderConfig(variant=VARIANTS[a.variant], T=a.iterations, alpha=a.alpha, delta=a.delta,
                                precision=native.F64 if a.precision == "f64" else native.F32,
@@ -436,20 +457,28 @@ def _gdbf_sweep(a, seed, world, rank, device, ck=None) -> int:
 
 
 def _fxms_sweep(a, seed, world, rank, device, ck=None) -> int:
-    """One SNR point after the other on fixed-point min-sum, frames sharded as above; the min-sum
-    stop rule (decodeMinSum.cpp:189). With --early-stop the frames report their iterations."""
+    """One SNR point after the other on fixed-point min-sum (--fxms) or its layered form (--fxlms),
+    frames sharded as above; the min-sum stop rule (decodeMinSum.cpp:189). With --early-stop the
+    frames report their iterations."""
     g = native.Graph.from_alist(a.alist)
     ctx = native.Context(g, device, a.batch)
-    s = _fxms_settings(a)
-    cfg = native.FxmsConfig(variant=VARIANTS[a.variant], T=a.iterations, early_stop=bool(a.early_stop),
-                            precision=native.F64 if a.precision == "f64" else native.F32, **s)
-    extra = [s["ymax"], float(s["qbits"]), float(s["msg_bits"])]
+    layered = bool(getattr(a, "fxlms", False))
+    s = _fxlms_settings(a) if layered else _fxms_settings(a)
+    cfg = (native.FxlmsConfig if layered else native.FxmsConfig)(
+        variant=VARIANTS[a.variant], T=a.iterations, early_stop=bool(a.early_stop),
+        precision=native.F64 if a.precision == "f64" else native.F32, **s)
+    extra = [s["ymax"], float(s["qbits"]), float(s["msg_bits"])] + ([float(s["app_bits"])] if layered else [])
     if a.variant == "nms":
         extra += [float(s["nms_num"]), float(s["nms_shift"])]
     elif a.variant == "oms":
         extra.append(float(s["beta"]))
-    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, ctx.fxms_sim_batch, ctx.fxms_sim_launch,
-                        ctx.fxms_kernel_info, extra, {"decoder": "fxms", "variant": a.variant, "schedule": a.schedule},
+    fns = (ctx.fxlms_sim_batch, ctx.fxlms_sim_launch, ctx.fxlms_kernel_info) if layered else \
+        (ctx.fxms_sim_batch, ctx.fxms_sim_launch, ctx.fxms_kernel_info)
+    # (--fxlms: the JSON line names the schedule the decoder runs; the checkpoint settings keep --schedule's value,
+    # "flooding", which --fxlms requires, and tell the two decoders apart by their "fxlms" key)
+    return _flip_points(a, seed, world, rank, device, ck, g, ctx, cfg, *fns, extra,
+                        {"decoder": "fxlms" if layered else "fxms", "variant": a.variant,
+                         "schedule": "layered" if layered else a.schedule},
                         stops=cfg.early_stop,
                         min_fe=a.min_frame_errors if a.min_frame_errors is not None else 40)
 

@@ -41,7 +41,9 @@ instance for the A/B of the two kernel shapes; where that is the library's own c
 wavefront shape is measured with --lib on `make hwgdbfvariant VFLAGS=-DLDPC_HWGDBF_FORCE_WAVE`),
 src/newstat.cpp:305-429 (the rstat_* lines: 200 frames x 100 attempts as scripts/redecode_statistics_802.3.sh
 runs them; *_wg forces the workgroup-per-attempt kernel). The fxms_* lines (fixed-point min-sum,
-fxms.hip) have no reference counterpart; nms_1944_* is the floating-point NMS beside them.
+fxms.hip) have no reference counterpart; nms_1944_* is the floating-point NMS beside them. The
+fxlms_* lines are its row-layered form (fxlms.hip) at app_bits = msg_bits + 1, written to
+profiles/fxlms_configs.jsonl beside the fxms_* lines of the same session.
 """
 import argparse
 import csv
@@ -137,6 +139,10 @@ for _snr, _es, _tag in ((1.5, False, ""), (3.0, True, "_es")):
         CONFIGS[f"fxms_1944_nms_m{_bits}{_tag}"] = dict(
             kind="fxms", code="80211n_1944_r12.alist", prec="f32", T=50, batch=65536, snr=_snr, msg_bits=_bits,
             early_stop=_es, what=f"fixed-point NMS 3/4 on 802.11n N=1944, msg_bits {_bits}, Q 5, T{'<=' if _es else '='}50")
+        CONFIGS[f"fxlms_1944_nms_m{_bits}{_tag}"] = dict(
+            kind="fxlms", code="80211n_1944_r12.alist", prec="f32", T=50, batch=65536, snr=_snr, msg_bits=_bits,
+            early_stop=_es, what=f"layered fixed-point NMS 3/4 on 802.11n N=1944, msg_bits {_bits}, app_bits {_bits + 1}, "
+                                 f"Q 5, T{'<=' if _es else '='}50")
     for _prec in ("f32", "f64"):
         CONFIGS[f"nms_1944_{_prec}{_tag}"] = dict(
             kind="minsum", code="80211n_1944_r12.alist", variant="nms", prec=_prec, T=50, batch=65536, snr=_snr,
@@ -231,6 +237,13 @@ class Workload:
             self.launch_fn = self.ctx.fxms_sim_launch
             info = self.ctx.fxms_kernel_info(self.cfg)
             self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
+        elif c["kind"] == "fxlms":
+            self.cfg = native.FxlmsConfig(variant=native.NMS, T=c["T"], qbits=5, msg_bits=c["msg_bits"],
+                                          app_bits=c["msg_bits"] + 1, nms_num=3, nms_shift=2, early_stop=c["early_stop"],
+                                          ymax=31 / 16, precision=prec)
+            self.launch_fn = self.ctx.fxlms_sim_launch
+            info = self.ctx.fxlms_kernel_info(self.cfg)
+            self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
         else:
             v = {"ms": dict(variant=native.MS), "nms": dict(variant=native.NMS, alpha=1.25),
                  "bp": dict(variant=native.BP),
@@ -288,7 +301,7 @@ def timed(name, reps, lib):
         fr, _ = w.ctx.rgdbf_sim_batch(w.c["snr"], 0.5, w.cfg, seed=1, stream_id=0, first_cw=0, batch=w.c["batch"])
         ph = w.native.rgdbf_phases(fr["iters"], w.c["T"], w.c["maxphase"])
         out["phase_split"] = [int(x) for x in np.bincount(ph, minlength=w.c["maxphase"] + 1)[1:]]
-    if w.c["kind"] in ("hwgdbf", "fxms"):
+    if w.c["kind"] in ("hwgdbf", "fxms", "fxlms"):
         out["lds_bytes_per_workgroup"] = w.lds_bytes
     m = lds_edges_cycles(w)
     if m:
