@@ -294,6 +294,18 @@ int  ldpc_ctx_pp_inreg_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t 
  * the stream. LDPC_ERR_UNSUPPORTED as above. No reference counterpart. */
 int  ldpc_ctx_pp_row_slots(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, uint16_t *cols, uint8_t *deg, int cap,
                            int *nslots);
+/* The workgroup the "rows_pp" kernel launches for cfg: info[2] = {threads per block (1024: 8
+ * check and 8 bit waves; 768: 8 check and 4 bit waves, the in-register schedule with 3 bit slots
+ * per thread on codes that fit the fixed-stride LDS layout), dynamic LDS bytes of the launch (ldpc_ctx_kernel_info's
+ * decoder state plus that layout's gaps)}. LDPC_ERR_UNSUPPORTED as above. Host-only. No
+ * reference counterpart. */
+int  ldpc_ctx_pp_block_info(ldpc_ctx *ctx, const ldpc_decoder_cfg *cfg, int32_t *info);
+/* The rule behind the 768-thread block: info[2] = {1 when the fixed-stride LDS layout holds a
+ * code of n_bits bits whose row schedule has e_pad padded edge slots (ldpc_ctx_row_sched_info's
+ * e_pad) -- (n_bits + 3) * 8 <= 16384, (e_pad + 64) * 8 <= 65520 and the whole layout within
+ * 160 KB -- else 0, the dynamic LDS bytes of that layout}. No context, no device call. No
+ * reference counterpart. */
+int  ldpc_pp_block_layout(int n_bits, int e_pad, int32_t *info);
 
 /* ---- kernel-selection options (ABI 10) ------------------------------- */
 /* The library picks the kernel for a cfg by itself (the reference fixes its
@@ -307,7 +319,8 @@ typedef enum {
     LDPC_OPT_ROWS32 = 2,           /* fp32 MS / NMS row graphs: 0 rows_pp pairs, 1 rows_fast pairs, 2 the row kernel */
     LDPC_OPT_PP_SLOTS = 3,         /* rows_pp row slots: 0 degree-aware (when the code admits them) with the   */
                                    /* paired rows' degree-2 bits in registers (when it has pairs), 1 plain,   */
-                                   /* 2 degree-aware with every bit in LDS                                    */
+                                   /* 2 degree-aware with every bit in LDS, 3 as 0 but always on the 16-wave  */
+                                   /* block (0 takes the 12-wave block where the code fits its LDS layout)    */
     LDPC_OPT_KERNEL = 4,           /* generic kernel: 0 auto, 1 lds, 2 flood (persistent), 3 global           */
     LDPC_OPT_FLOOD_MODE = 5,       /* codes beyond LDS: 0 one launch per phase, 1 the persistent kernel       */
     LDPC_OPT_FLOOD_MSG = 6,        /* phase flooding messages: 0 packed row state, 1 the c2v array            */

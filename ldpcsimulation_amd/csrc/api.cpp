@@ -124,7 +124,7 @@ bool option_value_ok(int option, int v)
     switch (option) {
     case LDPC_OPT_ROWS64:
     case LDPC_OPT_ROWS32: return v >= 0 && v <= 2;
-    case LDPC_OPT_PP_SLOTS: return v >= 0 && v <= 2;
+    case LDPC_OPT_PP_SLOTS: return v >= 0 && v <= 3;
     case LDPC_OPT_FLOOD_MODE:
     case LDPC_OPT_FLOOD_MSG:
     case LDPC_OPT_BP_KERNEL:
@@ -946,6 +946,27 @@ int ldpc_ctx_pp_inreg_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *in
     info[1] = ri ? ri->lds_edge_slots : rsi[9];
     info[2] = ri ? ri->e_used : p.rs->e_pad;
     info[3] = ri ? ri->cpt : p.rs->cpt;
+    return LDPC_OK;
+}
+
+int ldpc_pp_block_layout(int n_bits, int e_pad, int32_t *info)
+{
+    if (!info) return set_err(LDPC_ERR_INVALID, "null argument");
+    int bytes = 0;
+    info[0] = ldpc::pp_w12_layout(n_bits, e_pad, &bytes) ? 1 : 0;
+    info[1] = bytes;
+    return LDPC_OK;
+}
+
+int ldpc_ctx_pp_block_info(ldpc_ctx *c, const ldpc_decoder_cfg *cfg, int32_t *info)
+{
+    if (!info) return set_err(LDPC_ERR_INVALID, "null argument");
+    ldpc::LaunchPlan p;
+    RC_TRY(info_plan(c, cfg, p));
+    if (p.kernel != ldpc::Kernel::rows_pp || !p.rs)
+        return set_err(LDPC_ERR_UNSUPPORTED, "the ping-pong kernel does not decode this cfg (kernel %s)", p.name);
+    info[0] = p.threads;
+    info[1] = p.lds_bytes + p.cache_lds_bytes + p.pad_lds_bytes;
     return LDPC_OK;
 }
 

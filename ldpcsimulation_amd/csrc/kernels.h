@@ -103,6 +103,7 @@ struct LaunchPlan {
     int lds_bytes = 0;              // dynamic LDS per block that holds decoder state, as reported
     int layered_pos = 0;            // layered_global: P, the posteriors of the global slot cached in LDS,
     int cache_lds_bytes = 0;        //   and their dynamic LDS (P + the dummy slot, fp64 only); not reported
+    int pad_lds_bytes = 0;          // rows_pp on the 12-wave block: the gaps of its fixed-stride LDS layout; not reported
     int cw_per_block = 1;           // row kernels: codewords decoded together per thread (as reported)
     int blocks_per_cu = 0;          // as reported; sizes the grid of the kernels that work in global scratch
     int grid = 0;                   // blocks of the launch; flood_phase: resident slots K
@@ -212,8 +213,13 @@ hipError_t launch_redo(const DevGraph &g, const DecodeArgs &a, bool f64, const u
 // with the verified reciprocal, rows_fast_f32_ok). plan_rows_pp: as plan_rows_fast.
 // With PlanInput.rs_ppi (fp64, LDPC_OPT_PP_SLOTS 0) the launch is k_rows_ppi: the degree-2
 // bits that join a check thread's two rows stay in that thread's registers (graph.h
-// pp_pair_rows); the plan still describes the split schedule it is derived from.
+// pp_pair_rows); the plan still describes the split schedule it is derived from. Where the
+// code fits the fixed-stride LDS layout that launch is k_rows_ppw: a 768-thread block, the same
+// 8 check waves and 4 bit waves (LDPC_OPT_PP_SLOTS 3: k_rows_ppi always).
 bool plan_rows_pp(const PlanInput &in, LaunchPlan &p);
+// Whether k_rows_ppw's fixed-stride LDS layout holds a code of N bits whose split schedule has
+// e_pad padded edge slots; *lds_bytes (may be null): the dynamic LDS that layout takes.
+bool pp_w12_layout(int N, int e_pad, int *lds_bytes);
 // Bit slots per thread of the in-register schedule: 3 where the bits left fit 3 x 512 slots
 // in at most 24 groups (the bench code: 1458 bits, 23 groups), else 4 as in the schedule it
 // derives from. LDPC_PP_INREG_CPT = 4 (A/B builds): always 4.

@@ -236,7 +236,7 @@ int occupancy(const void *fn, int threads, int lds_bytes)
 
 hipError_t launch_fn(const LaunchPlan &p, void **args, hipStream_t s)
 {
-    const int lds = p.lds_bytes + p.cache_lds_bytes;
+    const int lds = p.lds_bytes + p.cache_lds_bytes + p.pad_lds_bytes;
     if (!p.fn || p.grid <= 0) return hipErrorInvalidValue;
     if (lds > 0) {
         const hipError_t e = hipFuncSetAttribute(p.fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);

@@ -195,6 +195,25 @@ namespace {
 #ifndef LDPC_PP_ONEPREM
 #define LDPC_PP_ONEPREM 1
 #endif
+// k_rows_ppw (the 12-wave block: 8 check waves as in k_rows_ppi, 4 bit waves that each take the
+// bit slots of two schedule threads; 168 VGPRs per wave instead of 128). It runs on the
+// in-register schedule with 3 bit slots per schedule thread (the 4-slot one was not measured
+// and stays on k_rows_ppi: 40 + 80 registers of read addresses and values) and on the fixed-stride LDS layout (pp_slots FIX): slot 1 of app / c2v lies a compile-time
+// distance behind slot 0, so the slot is selected by the immediate offset of the ds_read_b64 /
+// ds_write_b64 and one base serves both.
+// LDPC_PP_W12_UNP 1: a check row's gather and scatter byte addresses (slot 0's) are formed once
+// per launch and kept in registers; 0: from the packed 16-bit schedule per edge.
+#ifndef LDPC_PP_W12_UNP
+#define LDPC_PP_W12_UNP 1
+#endif
+// k_rows_ppw's bit role: reads of a lane's slot 0 (the largest group degree) / of
+// its other slots that are issued ahead of the first add; edges past them take one round trip each.
+#ifndef LDPC_PP_W12_K0
+#define LDPC_PP_W12_K0 12
+#endif
+#ifndef LDPC_PP_W12_K1
+#define LDPC_PP_W12_K1 4
+#endif
 #if LDPC_PP_SBASE && !defined(LDPC_CHECK)
 #define PP_ADDR8(DC, w, k, base, n, site) addr8<DC, true>(w, k, base)
 #else
@@ -280,13 +299,30 @@ struct PPSlots {
 // 16-byte aligned (the channel's ds_write_b128 pairs)
 __host__ __device__ constexpr int pp_slot_words(int N, int EA) { return (N + 3 + EA + 1) & ~1; }
 
-template <typename P>
+// The fixed-stride layout (k_rows_ppw): app[0] at 0, app[1] at kPPAppStride; behind them per slot
+// one word that holds +0 (what the bit role reads for an edge its bit-slot group does not have)
+// and the slot's c2v array of at most kPPC2vStride bytes, slot 1's word and array kPPC2vDist
+// bytes behind slot 0's (a ds instruction's offset field holds 16 bits); red[] behind c2v[1].
+constexpr uint32_t kPPAppStride = 16384, kPPC2vStride = 65520, kPPC2vDist = kPPC2vStride + 8;
+
+template <typename P, bool FIX = false>
 __device__ __forceinline__ PPSlots<P> pp_slots(unsigned char *smem, int N, int EA)
 {
     static_assert(sizeof(P) == 8, "one 8-byte LDS word per slot element");
     PPSlots<P> s;
-    const int SL = pp_slot_words(N, EA);
     P *b = reinterpret_cast<P *>(smem);
+    if constexpr (FIX) {
+#pragma unroll
+        for (int X = 0; X < 2; ++X) {
+            s.app[X] = b + X * (kPPAppStride / 8);
+            s.c2v[X] = b + (2 * kPPAppStride + 8 + X * kPPC2vDist) / 8;   // the +0 word is c2v[X][-1]
+            s.app_base[X] = lds_addr_of(s.app[X]);
+            s.c2v_base[X] = lds_addr_of(s.c2v[X]);
+        }
+        s.red = reinterpret_cast<int *>(s.c2v[1] + EA);
+        return s;
+    }
+    const int SL = pp_slot_words(N, EA);
 #pragma unroll
     for (int X = 0; X < 2; ++X) {
         s.app[X] = b + X * SL;
@@ -439,13 +475,15 @@ __device__ __forceinline__ void pp_channel(const DecodeArgs &a, const PPSlots<Pa
     }
 }
 
-// A wave's sum of per-lane counts 0..7, bit-sliced: three ballots and popcounts on the
+// A wave's sum of per-lane counts 0 .. 2^NB - 1, bit-sliced: NB ballots and popcounts on the
 // scalar unit instead of a cross-lane shuffle tree.
-__device__ __forceinline__ int wave_sum3(int x)
+template <int NB>
+__device__ __forceinline__ int wave_sum(int x)
 {
-    return __builtin_popcountll(__builtin_amdgcn_ballot_w64((x & 1) != 0)) +
-           2 * __builtin_popcountll(__builtin_amdgcn_ballot_w64((x & 2) != 0)) +
-           4 * __builtin_popcountll(__builtin_amdgcn_ballot_w64((x & 4) != 0));
+    int t = 0;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) t += (1 << b) * __builtin_popcountll(__builtin_amdgcn_ballot_w64((x & (1 << b)) != 0));
+    return t;
 }
 
 // Block sums of the step's (bit errors, uncoded errors, syndrome) per codeword and
@@ -455,11 +493,14 @@ __device__ __forceinline__ int wave_sum3(int x)
 // codeword (N <= 2048, rows_pp_supported), so its bit and uncoded errors are <= 4; a
 // check-role lane holds the 0/1 syndrome of its rows (and, k_rows_ppi, the error of its one
 // in-register bit) -- so each wave sums them by
-// ballots (wave_sum3; the syndrome is an OR) and lane 0 adds the wave's totals into
+// ballots (wave_sum; the syndrome is an OR) and lane 0 adds the wave's totals into
 // red[kPPRedSums ...] with LDS atomics: one barrier, and only thread 0 reads the totals
 // (it clears them for the next step).
 // WCHK: the check role's lanes carry bit errors too (the in-register bits, <= 1 per lane and codeword).
-template <int C, bool HB, bool WCHK = false>
+// CHU: they carry uncoded errors too (their share of the channel). NB: bits of the sliced sums --
+// 4 in k_rows_ppw, whose bit-role lanes hold up to 8 bit slots and, outside a plain step, two
+// Philox groups of each codeword (counts <= 8).
+template <int C, bool HB, bool WCHK = false, bool CHU = (LDPC_PP_CHAN_ALL || LDPC_PP_CHAN_SPLIT), int NB = 3>
 __device__ __forceinline__ void pp_account(const DecodeArgs &a, int *red, int grp, int (&sums)[6 * C], unsigned *redo,
                                            unsigned long long *acc)
 {
@@ -469,17 +510,17 @@ __device__ __forceinline__ void pp_account(const DecodeArgs &a, int *red, int gr
 #pragma unroll
         for (int q = 0; q < 2 * C; ++q) {
             if constexpr (HB) {
-                const int w = wave_sum3(sums[3 * q]), u = wave_sum3(sums[3 * q + 1]);
+                const int w = wave_sum<NB>(sums[3 * q]), u = wave_sum<NB>(sums[3 * q + 1]);
                 if (lane0 && w) atomicAdd(&tot[3 * q], w);
                 if (lane0 && u) atomicAdd(&tot[3 * q + 1], u);
             } else {
                 if (__builtin_amdgcn_ballot_w64(sums[3 * q + 2] != 0) && lane0) atomicAdd(&tot[3 * q + 2], 1);
                 if constexpr (WCHK) {
-                    const int w = wave_sum3(sums[3 * q]);
+                    const int w = wave_sum<NB>(sums[3 * q]);
                     if (lane0 && w) atomicAdd(&tot[3 * q], w);
                 }
-                if constexpr (LDPC_PP_CHAN_ALL || LDPC_PP_CHAN_SPLIT) {   // the check waves' share of the channel
-                    const int u = wave_sum3(sums[3 * q + 1]);
+                if constexpr (CHU) {   // the check waves' share of the channel
+                    const int u = wave_sum<NB>(sums[3 * q + 1]);
                     if (lane0 && u) atomicAdd(&tot[3 * q + 1], u);
                 }
             }
@@ -550,7 +591,11 @@ __device__ __forceinline__ bool pp_check_node(const Pack<F, C> (&xin)[DCA], Pack
 // staged yq (padding: +inf) and no scatter for them; 2 a check wave where some lanes hold
 // real edges there: both gathers and scatters are issued (the paired lanes' scatters go to
 // the dummy slot) and the in-register sum is selected per lane (rs.pair bit 0).
-template <typename F, int SRC, int DC0, int DC1, int CPT, int VAR, bool FDIV, int R, bool HB, int IR = 0>
+// W: waves of the block. 16: 8 check and 8 bit waves. 12 (k_rows_ppw): the same 8 check waves and
+// 4 bit waves; bit wave w holds the bit slots of schedule threads 64 w + lane and 64 (w + 4) + lane
+// (CPL = 2 CPT slots per lane, merged in non-increasing group degree), reads them in one round
+// trip (LDPC_PP_W12_K0 / K1), and a plain step's channel is spread over all 768 threads.
+template <typename F, int SRC, int DC0, int DC1, int CPT, int VAR, bool FDIV, int R, bool HB, int IR = 0, int W = 16>
 __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, const RowSched &rs,
                                         const PPSlots<Pack<F, PPCw<F>::C>> &s, unsigned *redo,
                                         unsigned long long *acc)
@@ -560,6 +605,14 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
     constexpr int DCX = 8;                    // schedule stride (rs.dc)
     constexpr int RR = R > 0 ? R : 1;   // array extents
     static_assert(DC0 <= DCX && DC1 <= DCX && (R == 0) == HB, "pp_role shape");
+    static_assert(W == 16 || W == 12, "pp_role block shape");
+    constexpr bool W12 = W == 12;
+    constexpr int NT = 64 * W, NBT = NT - kPPRole;   // threads of the block / of its bit role
+    constexpr int CPL = HB ? CPT * (kPPRole / NBT) : CPT;   // bit slots per lane
+    constexpr bool FIXL = W12;   // pp_slots FIX
+    constexpr bool UNP = FIXL && LDPC_PP_W12_UNP && R > 0 && sizeof(F) == 8 && LDPC_PP_EXP == 0;
+    constexpr bool SPLITCH = LDPC_PP_CHAN_SPLIT || W12;
+    static_assert(!UNP || LDPC_PP_PREFETCH, "unpacked addresses: both rows' gathers ahead of row 0");
     // IR needs LDPC_PP_NOB2 (yq staged canonical by the channel) and LDPC_PP_PREFETCH (both rows'
     // gathers ahead of row 0); plan_rows_pp picks k_rows_ppi only in builds that have both
     static_assert(IR == 0 || R == 2, "in-register bits: two rows per check thread");
@@ -599,6 +652,26 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             colw[0][L0 / 2] = (L0 & 1) ? (colw[0][L0 / 2] & 0xffffu) | ((uint32_t)N << 16)
                                        : (colw[0][L0 / 2] & 0xffff0000u) | (uint32_t)N;
     }
+    // UNP: slot 0's LDS byte address of every gather (ga) and scatter (sa) of the rows, formed once
+    // (the in-register edge of IR == 1 has neither); vin: the in-register bit (IR == 1: or N, a padding edge)
+    [[maybe_unused]] uint32_t ga[RR][DCX], sa[RR][DCX], vin = 0;
+    if constexpr (UNP) {
+        static_for<0, R>([&](auto rc) {
+            constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
+#pragma unroll
+            for (int k = 0; k < DCr - (IR == 1 ? 1 : 0); ++k) {
+                ga[r][k] = s.app_base[0] + 8u * (uint32_t)LDPC_CHK(u16_at<DCX>(colw[r], k), N + 3, CHK_PP_GATHER);
+                sa[r][k] = s.c2v_base[0] + 8u * (uint32_t)LDPC_CHK(u16_at<DCX>(posw[r], k), EA, CHK_PP_SCATTER);
+                // opaque: the compiler otherwise keeps 8 * entry and adds the array's base at every access
+                asm("" : "+v"(ga[r][k]), "+v"(sa[r][k]));
+            }
+        });
+        if constexpr (IR != 0) vin = (uint32_t)LDPC_CHK(u16_at<DCX>(colw[0], L0), N + 3, CHK_PP_GATHER);
+    }
+    [[maybe_unused]] auto inreg_col = [&]() -> int {
+        if constexpr (UNP) return (int)vin;
+        else return u16_at<DCX>(colw[0], L0);
+    };
     // IR: (yq + c2v_first) + c2v_second of slot X's in-register bit, from the staged yq `y`
     // and the messages the two rows sent last (prev): the bit node's sum (:452-476)
     [[maybe_unused]] auto inreg_sum = [&](auto Xc, const P &y) -> P {
@@ -613,14 +686,36 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
     };
     // bit slots of schedule thread bt
     const int bt = tid - kPPRole;
-    [[maybe_unused]] int vgb[CPT], vgd[CPT];
-    [[maybe_unused]] uint32_t vdst2[(CPT + 1) / 2] = {};
+    static_assert(!UNP || IR != 1 || LDPC_PP_INREG_Y, "unpacked addresses: the in-register bit's sample in registers");
+    [[maybe_unused]] int vgb[CPL], vgd[CPL];
+    [[maybe_unused]] uint32_t vdst2[(CPL + 1) / 2] = {};
+    [[maybe_unused]] uint32_t ra[CPL][LDPC_PP_W12_K0 > LDPC_PP_W12_K1 ? LDPC_PP_W12_K0 : LDPC_PP_W12_K1];   // W12: below
     if constexpr (HB) {
+        // the schedule entry of lane slot i. W12: the slots of schedule threads bt and bt + NBT (the
+        // bit-slot groups of two of the schedule's waves), merged by group degree -- wave-uniform, and
+        // non-increasing along each thread's slots (graph.cpp build_row_schedule)
+        int si[CPL];
+        if constexpr (W12) {
+            int pa = 0, pb = 0;
 #pragma unroll
-        for (int i = 0; i < CPT; ++i) {
-            const int c = rs.vn_col[bt * CPT + i];
+            for (int i = 0; i < CPL; ++i) {
+                const int ia = bt * CPT + (pa < CPT ? pa : CPT - 1), ib = (bt + NBT) * CPT + (pb < CPT ? pb : CPT - 1);
+                const int da = pa < CPT ? __builtin_amdgcn_readfirstlane((int)(rs.vn_info[ia] >> 24)) : -1;
+                const int db = pb < CPT ? __builtin_amdgcn_readfirstlane((int)(rs.vn_info[ib] >> 24)) : -1;
+                const bool ta = da >= db;
+                si[i] = ta ? ia : ib;
+                pa += ta ? 1 : 0;
+                pb += ta ? 0 : 1;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) si[i] = bt * CPT + i;
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int c = rs.vn_col[si[i]];
             vdst2[i / 2] |= (uint32_t)(c == 0xffff ? N + 1 : c) << (16 * (i & 1));
-            const uint32_t info = rs.vn_info[bt * CPT + i];
+            const uint32_t info = rs.vn_info[si[i]];
             vgb[i] = __builtin_amdgcn_readfirstlane((int)(info & 0xffffu) - lane);
             vgd[i] = __builtin_amdgcn_readfirstlane((int)(info >> 24));
         }
@@ -628,9 +723,23 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         P z;
 #pragma unroll
         for (int c = 0; c < C; ++c) z.v[c] = F(0);
+        if constexpr (W12) {
+            // slot 0's LDS byte address of edge k of lane slot i, or of the slot's +0 word (c2v[-1],
+            // never written again) where the group has no edge k
+            if (tid == kPPRole + 2) s.c2v[0][-1] = s.c2v[1][-1] = z;
+            const int ln0 = lane;
 #pragma unroll
-        for (int i = 0; i < CPT; ++i) {
-            const int dg = (int)((rs.vn_info[bt * CPT + i] >> 16) & 0xffu);
+            for (int i = 0; i < CPL; ++i)
+#pragma unroll
+                for (int k = 0; k < (i == 0 ? LDPC_PP_W12_K0 : LDPC_PP_W12_K1); ++k) {
+                    const uint32_t e = (uint32_t)LDPC_CHK(k < vgd[i] ? vgb[i] + ln0 + k * 64 : 0, EA, CHK_PP_BIT_READ);
+                    ra[i][k] = k < vgd[i] ? s.c2v_base[0] + 8u * e : s.c2v_base[0] - 8u;
+                    asm("" : "+v"(ra[i][k]));   // opaque: kept as formed, not rebuilt from the group's base at every read
+                }
+        }
+#pragma unroll
+        for (int i = 0; i < CPL; ++i) {
+            const int dg = (int)((rs.vn_info[si[i]] >> 16) & 0xffu);
             const int base = vgb[i] + lane, gd = vgd[i];
             for (int k = dg; k < gd; ++k) {
                 const int e = LDPC_CHK(base + k * 64, EA, CHK_PP_BIT_READ);
@@ -666,27 +775,26 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         for (int q = 0; q < 2 * C; ++q) unc[q] = wdec[q] = 0;
         [[maybe_unused]] unsigned chan_bad = 0;   // LDPC_PP_NOB2: slots with an input past the premise
         if constexpr (LDPC_PP_CHAN_ALL && !HB) {   // the check waves take Philox groups too
-            if (!(LDPC_PP_TAILEXP & 1)) pp_channel<F, SRC>(a, s, N, grp, unc, tid, 2 * kPPRole, &chan_bad);
+            if (!(LDPC_PP_TAILEXP & 1)) pp_channel<F, SRC>(a, s, N, grp, unc, tid, NT, &chan_bad);
         }
-        [[maybe_unused]] const bool split = LDPC_PP_CHAN_SPLIT && SRC == SRC_PHILOX && LDPC_PP_NOB2 &&
+        [[maybe_unused]] const bool split = SPLITCH && SRC == SRC_PHILOX && LDPC_PP_NOB2 &&
                                             !(LDPC_PP_TAILEXP & 1) && pp_plain_step(a, N, grp, C);
-        if constexpr (LDPC_PP_CHAN_SPLIT && !HB) {   // the check waves' share of a plain step
-            if (split) pp_channel_plain<F>(a, s, N, grp, unc, tid, 2 * kPPRole, &chan_bad);
+        if constexpr (SPLITCH && !HB) {   // the check waves' share of a plain step
+            if (split) pp_channel_plain<F>(a, s, N, grp, unc, tid, NT, &chan_bad);
         }
         if constexpr (HB) {
-            if (LDPC_PP_CHAN_SPLIT && split) {
-                pp_channel_plain<F>(a, s, N, grp, unc, tid, 2 * kPPRole, &chan_bad);
+            if (SPLITCH && split) {
+                pp_channel_plain<F>(a, s, N, grp, unc, tid, NT, &chan_bad);
             } else if (!(LDPC_PP_TAILEXP & 1)) {
-                pp_channel<F, SRC>(a, s, N, grp, unc, LDPC_PP_CHAN_ALL ? tid : bt, LDPC_PP_CHAN_ALL ? 2 * kPPRole : kPPRole,
-                                   &chan_bad);
+                pp_channel<F, SRC>(a, s, N, grp, unc, LDPC_PP_CHAN_ALL ? tid : bt, LDPC_PP_CHAN_ALL ? NT : NBT, &chan_bad);
             } else {   // timing only: a constant channel
                 for (int q = 0; q < 2 * C; ++q) unc[q] = 0;
-                for (int v = bt; v < N; v += kPPRole)
+                for (int v = bt; v < N; v += NBT)
                     for (int c = 0; c < C; ++c) s.app[0][v].v[c] = s.app[1][v].v[c] = F(1);
             }
         }
         PP_SYNC_STAMPED(1);   // B1: channel staged
-        [[maybe_unused]] P yq[2][CPT];
+        [[maybe_unused]] P yq[2][CPL];
         if constexpr (R > 0) {
 #pragma unroll
             for (int X = 0; X < 2; ++X)
@@ -697,7 +805,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 #pragma unroll
                         for (int c = 0; c < C; ++c) prev[X][r][k].v[c] = F(0);
         }
-        if constexpr ((LDPC_PP_CHAN_SPLIT || (LDPC_PP_CHAN_ALL && LDPC_PP_NOB2)) && !HB) {   // the check waves' share of the channel's flags
+        if constexpr ((SPLITCH || (LDPC_PP_CHAN_ALL && LDPC_PP_NOB2)) && !HB) {   // the check waves' share of the channel's flags
             if (__builtin_amdgcn_ballot_w64(chan_bad != 0)) {
                 if (chan_bad & 1u) s.red[0] = 1;
                 if (chan_bad & 2u) s.red[1] = 1;
@@ -715,14 +823,14 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 #pragma unroll
             for (int X = 0; X < 2; ++X)
 #pragma unroll
-                for (int i = 0; i < CPT; ++i)
+                for (int i = 0; i < CPL; ++i)
                     yq[X][i] = s.app[X][LDPC_CHK(vdst(i) < N ? vdst(i) : N + 2, N + 3, CHK_PP_APP_WRITE)];
         } else if constexpr (HB) {
 #pragma unroll
             for (int X = 0; X < 2; ++X) {
                 bool in_ok = true;
 #pragma unroll
-                for (int i = 0; i < CPT; ++i) {
+                for (int i = 0; i < CPL; ++i) {
                     const P st = s.app[X][LDPC_CHK(vdst(i) <= N ? vdst(i) : 0, N + 3, CHK_PP_APP_WRITE)];
 #pragma unroll
                     for (int c = 0; c < C; ++c) {
@@ -732,7 +840,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                     }
                 }
 #pragma unroll
-                for (int i = 0; i < CPT; ++i) s.app[X][LDPC_CHK(vdst(i), N + 3, CHK_PP_APP_WRITE)] = yq[X][i];   // v2c = yq on the first pass (:364-370)
+                for (int i = 0; i < CPL; ++i) s.app[X][LDPC_CHK(vdst(i), N + 3, CHK_PP_APP_WRITE)] = yq[X][i];   // v2c = yq on the first pass (:364-370)
                 if (!in_ok) s.red[X] = 1;
             }
             P inf, zero;
@@ -758,7 +866,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                     const int q = Y * C + c;
                     int e = 0;
 #pragma unroll
-                    for (int i = 0; i < CPT; ++i) e += (vdst(i) < N && !(post[i].v[c] > F(0))) ? 1 : 0;   // :471-474
+                    for (int i = 0; i < CPL; ++i) e += (vdst(i) < N && !(post[i].v[c] > F(0))) ? 1 : 0;   // :471-474
                     w[q] = grp * 2 * C + q < a.batch ? e : 0;
                 }
                 return;
@@ -773,7 +881,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                                                    : nullptr);
                 int e = 0;
 #pragma unroll
-                for (int i = 0; i < CPT; ++i) {
+                for (int i = 0; i < CPL; ++i) {
                     const int v = vdst(i);
                     if (v < N) {
                         const int d = post[i].v[c] > F(0) ? 1 : -1;   // :471-474
@@ -789,13 +897,13 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
         [[maybe_unused]] P yreg[2];   // LDPC_PP_INREG_Y: the in-register bit's staged sample per slot
         if constexpr (YREG) {
 #pragma unroll
-            for (int X = 0; X < 2; ++X) yreg[X] = s.app[X][LDPC_CHK(u16_at<DCX>(colw[0], L0), N + 3, CHK_PP_GATHER)];
+            for (int X = 0; X < 2; ++X) yreg[X] = s.app[X][LDPC_CHK(inreg_col(), N + 3, CHK_PP_GATHER)];
         }
         // IR: the in-register bit's final posterior per slot (inreg_final, once the slot's last check phase is done)
         [[maybe_unused]] P ipost[2];
         [[maybe_unused]] auto inreg_final = [&](auto Xc) {
             constexpr int X = decltype(Xc)::value;
-            ipost[X] = inreg_sum(Xc, YREG ? yreg[X] : s.app[X][LDPC_CHK(u16_at<DCX>(colw[0], L0), N + 3, CHK_PP_GATHER)]);
+            ipost[X] = inreg_sum(Xc, YREG ? yreg[X] : s.app[X][LDPC_CHK(inreg_col(), N + 3, CHK_PP_GATHER)]);
         };
         // Syndrome of slot X's codeword c (rows; padding edges read +inf: parity 0; rows past M skipped)
         auto syndrome = [&](int X, int c) -> int {
@@ -807,7 +915,9 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 #pragma unroll
                     for (int k = 0; k < DCr; ++k) {
                         if (IR == 1 && k == DCr - 1) continue;   // the in-register edge: below
-                        const int neg = (s.app[X][LDPC_CHK(u16_at<DCX>(colw[r], k), N + 3, CHK_PP_GATHER)].v[c] > F(0)) ? 0 : 1;
+                        int neg;
+                        if constexpr (UNP) neg = (lds_at<P>(ga[r][k] + (X ? kPPAppStride : 0u)).v[c] > F(0)) ? 0 : 1;
+                        else neg = (s.app[X][LDPC_CHK(u16_at<DCX>(colw[r], k), N + 3, CHK_PP_GATHER)].v[c] > F(0)) ? 0 : 1;
                         par ^= (IR == 2 && k == DCr - 1 && has) ? 0 : neg;
                     }
                     if constexpr (IR != 0) par ^= (has && !(ipost[X].v[c] > F(0))) ? 1 : 0;
@@ -824,17 +934,25 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             [[maybe_unused]] P xin[RR][DCX];
             if constexpr (R > 0) {
                 if (rows && LDPC_PP_EXP != 2) {
+                    if constexpr (!UNP) {
 #pragma unroll
-                    for (int r = 0; r < R; ++r)
+                        for (int r = 0; r < R; ++r)
 #pragma unroll
-                        for (int q = 0; q < DCX / 2; ++q) asm volatile("" : "+v"(colw[r][q]), "+v"(posw[r][q]));
-                    const uint32_t ab = s.app_base[X];
+                            for (int q = 0; q < DCX / 2; ++q) asm volatile("" : "+v"(colw[r][q]), "+v"(posw[r][q]));
+                    }
+                    // FIXL: slot 0's base, the slot in the instruction's offset field
+                    [[maybe_unused]] const uint32_t ab = s.app_base[FIXL ? 0 : X];
+                    constexpr uint32_t aoff = FIXL ? X * kPPAppStride : 0u;
                     static_for<0, (LDPC_PP_PREFETCH ? R : 1)>([&](auto rc) {
                         constexpr int r = decltype(rc)::value, DCr = r == 0 ? DC0 : DC1;
 #pragma unroll
-                        for (int k = 0; k < DCr - (IR == 1 && (r == 1 || YREG) ? 1 : 0); ++k)   // IR == 1: row 1's last edge is row 0's
-                            xin[r][k] = lds_at<P>((LDPC_PP_EXP == 5 || LDPC_PP_EXP == 7) ? ab + 8u * (uint32_t)(lane + 64 * (k + 8 * r))
-                                                                                         : PP_ADDR8(DCX, colw[r], k, ab, N + 3, CHK_PP_GATHER));
+                        for (int k = 0; k < DCr - (IR == 1 && (r == 1 || YREG) ? 1 : 0); ++k) {   // IR == 1: row 1's last edge is row 0's
+                            if constexpr (UNP)
+                                xin[r][k] = lds_at<P>(ga[r][k] + aoff);
+                            else
+                                xin[r][k] = lds_at<P>(((LDPC_PP_EXP == 5 || LDPC_PP_EXP == 7) ? ab + 8u * (uint32_t)(lane + 64 * (k + 8 * r))
+                                                                                              : PP_ADDR8(DCX, colw[r], k, ab, N + 3, CHK_PP_GATHER)) + aoff);
+                        }
                     });
                     if constexpr (LDPC_PP_GATHER_FIRST && LDPC_PP_PREFETCH) {
                         // every gather of the interval issued ahead of the check-node arithmetic
@@ -848,21 +966,48 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                 if (LDPC_PP_BITDELAY > 0) __builtin_amdgcn_s_sleep(LDPC_PP_BITDELAY);
                 if (bits && LDPC_PP_EXP != 1) {   // bit nodes: sum = yq + c2v in nlist order (:452-476)
 #pragma unroll
-                    for (int q = 0; q < (CPT + 1) / 2; ++q) asm volatile("" : "+v"(vdst2[q]));
-                    P sum[CPT];
+                    for (int q = 0; q < (CPL + 1) / 2; ++q) asm volatile("" : "+v"(vdst2[q]));
+                    P sum[CPL];
 #pragma unroll
-                    for (int i = 0; i < CPT; ++i) sum[i] = yq[Y][i];
-                    int k = 0;
+                    for (int i = 0; i < CPL; ++i) sum[i] = yq[Y][i];
                     const int ln = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-                    vn_phases<F, C, CPT, CPT>(s.c2v[Y] + ln, vgb, vgd, k, sum, LDPC_CHK_LIM(EA - ln), CHK_PP_BIT_READ);
+                    if constexpr (W12) {
+                        // Every read of the interval ahead of the first add: edges k < K0 of slot 0 and
+                        // k < K1 of the other slots, from the addresses formed once per launch (ra: an
+                        // edge past its group's degree reads the slot's +0 word, and adding +0 changes no
+                        // sum), the slot in the offset field; then the adds, per slot in edge order (nlist
+                        // order, as vn_phases). One basic block, one LDS round trip.
+                        constexpr int K0 = LDPC_PP_W12_K0, K1 = LDPC_PP_W12_K1;
+                        const P *cv = s.c2v[Y] + ln;
+                        [[maybe_unused]] const int lim = LDPC_CHK_LIM(EA - ln);
+                        P rd[CPL][K0 > K1 ? K0 : K1];
 #pragma unroll
-                    for (int i = 0; i < CPT; ++i) s.app[Y][LDPC_CHK(vdst(i), N + 3, CHK_PP_APP_WRITE)] = sum[i];
+                        for (int i = 0; i < CPL; ++i)
+#pragma unroll
+                            for (int k = 0; k < (i == 0 ? K0 : K1); ++k) rd[i][k] = lds_at<P>(ra[i][k] + Y * kPPC2vDist);
+#pragma unroll
+                        for (int k = 0; k < (K0 > K1 ? K0 : K1); ++k)
+#pragma unroll
+                            for (int i = 0; i < CPL; ++i)
+                                if (k < (i == 0 ? K0 : K1)) padd<false>(sum[i], rd[i][k]);
+                        // group degrees past K0 / K1 (none in the bench code): one round trip per edge
+#pragma unroll
+                        for (int i = 0; i < CPL; ++i)
+                            for (int k = (i == 0 ? K0 : K1); k < vgd[i]; ++k)
+                                padd<false>(sum[i], cv[LDPC_CHK(vgb[i] + k * 64, lim, CHK_PP_BIT_READ)]);
+                    } else {
+                        int k = 0;
+                        vn_phases<F, C, CPL, CPL>(s.c2v[Y] + ln, vgb, vgd, k, sum, LDPC_CHK_LIM(EA - ln), CHK_PP_BIT_READ);
+                    }
+#pragma unroll
+                    for (int i = 0; i < CPL; ++i) s.app[Y][LDPC_CHK(vdst(i), N + 3, CHK_PP_APP_WRITE)] = sum[i];
                     if (TF && last) decide(Y, sum, wdec);   // slot Y's final pass
                 }
             }
             if constexpr (R > 0) {
                 if (rows && LDPC_PP_EXP != 2) {
-                    const uint32_t ab = s.app_base[X], cb = s.c2v_base[X];
+                    [[maybe_unused]] const uint32_t ab = s.app_base[X], cb = s.c2v_base[FIXL ? 0 : X];
+                    constexpr uint32_t coff = FIXL ? X * kPPC2vDist : 0u;
                     if constexpr (IR != 0) {   // the in-register bit's posterior in place of both rows' last gather
                         if constexpr (YREG) xin[0][L0] = yreg[X];
                         const P sum = inreg_sum(Xc, xin[0][L0]);
@@ -887,10 +1032,12 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
                         // the scatter of edge k into the bit-slot layout (experiments: none, or lane-contiguous)
                         auto store = [&](int k, const P &m) {
                             if (IR == 1 && k == DCr - 1) return;   // in-register (k is a constant once inlined)
-                            if constexpr (LDPC_PP_EXP != 4)
-                                lds_put<P>((LDPC_PP_EXP == 6 || LDPC_PP_EXP == 7)
-                                               ? cb + 8u * (uint32_t)(lane + 64 * ((k + 8 * r + 16 * (tid >> 6)) % 112))
-                                               : PP_ADDR8(DCX, posw[r], k, cb, EA, CHK_PP_SCATTER),
+                            if constexpr (UNP)
+                                lds_put<P>(sa[r][k] + coff, m);
+                            else if constexpr (LDPC_PP_EXP != 4)
+                                lds_put<P>(((LDPC_PP_EXP == 6 || LDPC_PP_EXP == 7)
+                                                ? cb + 8u * (uint32_t)(lane + 64 * ((k + 8 * r + 16 * (tid >> 6)) % 112))
+                                                : PP_ADDR8(DCX, posw[r], k, cb, EA, CHK_PP_SCATTER)) + coff,
                                            m);
                         };
                         if constexpr (LDPC_PP_EXP == 3) {
@@ -962,7 +1109,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
 
         if (LDPC_PP_TAILEXP & 2) {   // timing only: no syndrome, decisions or error weights
             int sums[6 * C] = {};
-            pp_account<C, HB, IR != 0>(a, s.red, grp, sums, redo, acc);
+            pp_account<C, HB, IR != 0, SPLITCH || LDPC_PP_CHAN_ALL, W12 ? 4 : 3>(a, s.red, grp, sums, redo, acc);
             continue;
         }
         // syndrome and decisions / error weight of the step's codewords (what the last
@@ -972,9 +1119,9 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             if (!fused) {
 #pragma unroll
                 for (int X = 0; X < 2; ++X) {
-                    P post[CPT];
+                    P post[CPL];
 #pragma unroll
-                    for (int i = 0; i < CPT; ++i) post[i] = s.app[X][LDPC_CHK(vdst(i) <= N ? vdst(i) : 0, N + 3, CHK_PP_APP_WRITE)];
+                    for (int i = 0; i < CPL; ++i) post[i] = s.app[X][LDPC_CHK(vdst(i) <= N ? vdst(i) : 0, N + 3, CHK_PP_APP_WRITE)];
                     decide(X, post, wdec);
                 }
             }
@@ -983,7 +1130,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             // the in-register bit: posterior, decision and error weight by its check thread (:270, :382-393)
             inreg_final(std::integral_constant<int, 0>());
             inreg_final(std::integral_constant<int, 1>());
-            const int v = u16_at<DCX>(colw[0], L0);
+            const int v = inreg_col();
             if (has && v < N) {   // IR == 1: a padding edge's index is N
 #pragma unroll
                 for (int q = 0; q < 2 * C; ++q) {
@@ -1011,7 +1158,7 @@ __device__ __forceinline__ void pp_role(const DecodeArgs &a, const DevGraph &g, 
             }
         }
         PP_STAMP_ACC(5);
-        pp_account<C, HB, IR != 0>(a, s.red, grp, sums, redo, acc);
+        pp_account<C, HB, IR != 0, SPLITCH || LDPC_PP_CHAN_ALL, W12 ? 4 : 3>(a, s.red, grp, sums, redo, acc);
     }
     PP_STAMP_OUT()
 }
@@ -1031,15 +1178,17 @@ LDPC_CHECK_TU(rows_pp)
 // 8-edge row. Otherwise every row runs the 8-edge check node.
 // INREG (k_rows_ppi; SPLIT): rs is the in-register schedule, and each check wave runs the role
 // rs.pair names for it (pp_role IR 1 or 2).
-template <typename F, int SRC, int CPT, int VAR, bool FDIV, bool SPLIT, bool INREG>
+// W: the block's waves (pp_role): 16, or 12 (k_rows_ppw; INREG).
+template <typename F, int SRC, int CPT, int VAR, bool FDIV, bool SPLIT, bool INREG, int W = 16>
 __device__ __forceinline__ void pp_kernel(const DecodeArgs &a, const DevGraph &g, const RowSched &rs, unsigned *redo)
 {
     static_assert(!INREG || SPLIT, "in-register bits come with the degree-aware row slots");
+    static_assert(W == 16 || INREG, "the 12-wave block runs the in-register schedule");
     using P = Pack<F, PPCw<F>::C>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 #pragma unroll
     for (int i = 0; i < LDPC_PP_ENTRY_NOPS; ++i) asm volatile("s_nop 0");
-    const PPSlots<P> s = pp_slots<P>(smem, g.N, rs.e_pad + 64);
+    const PPSlots<P> s = pp_slots<P, W == 12>(smem, g.N, rs.e_pad + 64);
     unsigned long long *acc = reinterpret_cast<unsigned long long *>(s.red + kPPRedAcc);   // thread 0's block totals
     if (threadIdx.x == 0) {
         s.red[0] = s.red[1] = 0;
@@ -1062,13 +1211,13 @@ __device__ __forceinline__ void pp_kernel(const DecodeArgs &a, const DevGraph &g
     if constexpr (INREG) {
         const bool pure = low && __builtin_amdgcn_readfirstlane((int)rs.pair[kPPRole + (low ? wave : 0)]) != 0;
         if (!low)
-            pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 0, true>(a, g, rs, s, redo, acc);
+            pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 0, true, 0, W>(a, g, rs, s, redo, acc);
         else if (wave >= kPPRole / 128) {
-            if (pure) pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 1>(a, g, rs, s, redo, acc);
-            else pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 2>(a, g, rs, s, redo, acc);
+            if (pure) pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 1, W>(a, g, rs, s, redo, acc);
+            else pp_role<F, SRC, 7, 7, CPT, VAR, FDIV, 2, false, 2, W>(a, g, rs, s, redo, acc);
         } else {
-            if (pure) pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 1>(a, g, rs, s, redo, acc);
-            else pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 2>(a, g, rs, s, redo, acc);
+            if (pure) pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 1, W>(a, g, rs, s, redo, acc);
+            else pp_role<F, SRC, 7, 8, CPT, VAR, FDIV, 2, false, 2, W>(a, g, rs, s, redo, acc);
         }
     } else if (!low)
         pp_role<F, SRC, 8, 8, CPT, VAR, FDIV, 0, true>(a, g, rs, s, redo, acc);
@@ -1099,6 +1248,14 @@ __global__ __launch_bounds__(2 * kPPRole) void k_rows_ppi(DecodeArgs a, DevGraph
     pp_kernel<F, SRC, CPT, VAR, FDIV, true, true>(a, g, rs, redo);
 }
 
+// The 12-wave block (the header of pp_role): the same in-register schedule, 8 check waves and 4 bit
+// waves, the fixed-stride LDS layout (pp_slots FIX). fp64 slots only.
+template <typename F, int SRC, int CPT, int VAR, bool FDIV>
+__global__ __launch_bounds__(kPPRole + kPPRole / 2) void k_rows_ppw(DecodeArgs a, DevGraph g, RowSched rs, unsigned *redo)
+{
+    pp_kernel<F, SRC, CPT, VAR, FDIV, true, true, 12>(a, g, rs, redo);
+}
+
 static int rows_pp_lds_bytes(const DevGraph &g, const RowSched &rs)
 {
     return (int)(2 * (size_t)pp_slot_words(g.N, rs.e_pad + 64) * 8 + kPPRedInts * sizeof(int));
@@ -1112,21 +1269,47 @@ static bool rows_pp_supported(const DevGraph &g, const RowSched &rs)
            g.N <= 4 * kPPRole && g.N + 3 <= 0xffff && rows_pp_lds_bytes(g, rs) <= 160 * 1024;
 }
 
-template <typename F, int SRC, int VAR, bool FDIV>
-static const void *pp_fn_t(const RowSched &rs)
+// Dynamic LDS of k_rows_ppw: the fixed-stride layout (pp_slots FIX) with red[] behind slot 1's c2v.
+static size_t rows_ppw_lds_bytes(const RowSched &rs)
 {
-    if constexpr (sizeof(F) == 8)   // fp32 pairs measured slower with in-register bits: fp64 only
+    return 2 * (size_t)kPPAppStride + 8 + kPPC2vDist + (size_t)(rs.e_pad + 64) * 8 + kPPRedInts * sizeof(int);
+}
+
+// k_rows_ppw decodes what k_rows_ppi does whenever the fixed-stride layout holds the code: both
+// app arrays within their stride, a c2v array within the reach of a ds offset field, and all of
+// it in the 160 KB of a workgroup.
+bool pp_w12_layout(int N, int e_pad, int *lds_bytes)
+{
+    RowSched rs{};
+    rs.e_pad = e_pad;
+    const size_t bytes = rows_ppw_lds_bytes(rs);
+    if (lds_bytes) *lds_bytes = (int)std::min<size_t>(bytes, 0x7fffffff);
+    return N >= 0 && e_pad >= 0 && ((size_t)N + 3) * 8 <= kPPAppStride && ((size_t)e_pad + 64) * 8 <= kPPC2vStride &&
+           bytes <= kMaxLds;
+}
+
+static bool rows_ppw_supported(const DevGraph &g, const RowSched &rs)
+{
+    return rs.cpt == 3 && pp_w12_layout(g.N, rs.e_pad, nullptr);
+}
+
+template <typename F, int SRC, int VAR, bool FDIV>
+static const void *pp_fn_t(const RowSched &rs, bool w12)
+{
+    if constexpr (sizeof(F) == 8) {   // fp32 pairs measured slower with in-register bits: fp64 only
+        if (rs.pair && w12) return (const void *)k_rows_ppw<F, SRC, 3, VAR, FDIV>;   // rows_ppw_supported: cpt 3
         if (rs.pair)
             return rs.cpt == 3 ? (const void *)k_rows_ppi<F, SRC, 3, VAR, FDIV> : (const void *)k_rows_ppi<F, SRC, 4, VAR, FDIV>;
+    }
     return rs.dc_low == 7 ? (const void *)k_rows_pp<F, SRC, 4, VAR, FDIV, true>
                           : (const void *)k_rows_pp<F, SRC, 4, VAR, FDIV, false>;
 }
 
-static const void *pp_fn(const RowSched &rs, const DecodeArgs &a, bool f64)
+static const void *pp_fn(const RowSched &rs, const DecodeArgs &a, bool f64, bool w12)
 {
     const bool given = a.src == SRC_GIVEN;
 #define LDPC_PP_SRC(FT, VARV, FD) \
-    return given ? pp_fn_t<FT, SRC_GIVEN, VARV, FD>(rs) : pp_fn_t<FT, SRC_PHILOX, VARV, FD>(rs);
+    return given ? pp_fn_t<FT, SRC_GIVEN, VARV, FD>(rs, w12) : pp_fn_t<FT, SRC_PHILOX, VARV, FD>(rs, w12);
     if (!f64) {   // fp32 pairs: MS, or NMS with the verified reciprocal (rows_fast_f32_ok)
         if (a.variant == V_MS) { LDPC_PP_SRC(float, V_MS, false) }
         if (a.variant == V_NMS && a.nms_fast) { LDPC_PP_SRC(float, V_NMS, false) }
@@ -1146,11 +1329,15 @@ bool plan_rows_pp(const PlanInput &in, LaunchPlan &p)
     // (LDPC_OPT_PP_SLOTS = 1, tests / A/B: always the row kernel's slots).
     // fp64, LDPC_OPT_PP_SLOTS = 0 on a code with row pairs: k_rows_ppi on the in-register schedule
     // derived from the degree-aware one (the same LDS partition; the plan reports the latter);
-    // 2: every bit in LDS on the degree-aware slots.
-    const RowSched *rs = in.rs_pp && opt(LDPC_OPT_PP_SLOTS) != 1 ? in.rs_pp : in.rs;
+    // 2: every bit in LDS on the degree-aware slots. The in-register schedule runs on the 12-wave
+    // block (k_rows_ppw) where its LDS layout holds the code (rows_ppw_supported); 3: as 0 on the
+    // 16-wave block (k_rows_ppi) always. The plan's lds_bytes stays the decoder state's (what the
+    // 16-wave layout takes); the fixed-stride layout's gaps are pad_lds_bytes.
+    const int slots = opt(LDPC_OPT_PP_SLOTS);
+    const RowSched *rs = in.rs_pp && slots != 1 ? in.rs_pp : in.rs;
     if (!rows_pp_supported(in.g, *rs)) return false;
     const RowSched *ri = nullptr;
-    if (in.f64 && LDPC_PP_NOB2 && LDPC_PP_PREFETCH && rs == in.rs_pp && in.rs_ppi && opt(LDPC_OPT_PP_SLOTS) == 0 &&
+    if (in.f64 && LDPC_PP_NOB2 && LDPC_PP_PREFETCH && rs == in.rs_pp && in.rs_ppi && (slots == 0 || slots == 3) &&
         rs->dc_low == 7 && in.rs_ppi->pair && in.rs_ppi->e_pad == rs->e_pad && rows_pp_supported(in.g, *in.rs_ppi))
         ri = in.rs_ppi;
     p.kernel = Kernel::rows_pp;
@@ -1158,10 +1345,12 @@ bool plan_rows_pp(const PlanInput &in, LaunchPlan &p)
     p.redo = true;
     p.rs = rs;
     p.rs_inreg = ri;
-    p.fn = pp_fn(ri ? *ri : *rs, in.a, in.f64);
-    p.threads = 2 * kPPRole;
+    const bool w12 = ri && slots == 0 && rows_ppw_supported(in.g, *ri);
+    p.fn = pp_fn(ri ? *ri : *rs, in.a, in.f64, w12);
+    p.threads = w12 ? kPPRole + kPPRole / 2 : 2 * kPPRole;
     p.lds_bytes = rows_pp_lds_bytes(in.g, *rs);
-    p.blocks_per_cu = 1;   // one 1024-thread block per CU
+    p.pad_lds_bytes = w12 ? (int)rows_ppw_lds_bytes(*ri) - p.lds_bytes : 0;
+    p.blocks_per_cu = 1;   // one block per CU
     const int CW = 2 * (in.f64 ? PPCw<double>::C : PPCw<float>::C);
     p.grid = std::min(in.num_cus, (in.a.batch + CW - 1) / CW);
     return true;

@@ -31,7 +31,8 @@ OPTIONS = {"rows64": 1, "rows32": 2, "pp_slots": 3, "kernel": 4, "flood_mode": 5
 EMS_OPTIONS = ("ems_threads", "ems_swizzle")
 # symbolic values of the kernel-choice options
 OPTION_VALUES = {"rows64": {"pp": 0, "fast": 1, "rows": 2}, "rows32": {"pp": 0, "fast": 1, "rows": 2},
-                 "pp_slots": {"split": 0, "plain": 1, "split_lds": 2}, "kernel": {"auto": 0, "lds": 1, "flood": 2, "global": 3},
+                 "pp_slots": {"split": 0, "plain": 1, "split_lds": 2, "split_w16": 3},
+                 "kernel": {"auto": 0, "lds": 1, "flood": 2, "global": 3},
                  "flood_mode": {"phase": 0, "persistent": 1}, "flood_msg": {"packed": 0, "c2v": 1},
                  "bp_kernel": {"rows": 0, "generic": 1}, "gdbf_kernel": {"rows": 0, "generic": 1},
                  "ddbmp_kernel": {"rows": 0, "generic": 1},
@@ -388,6 +389,8 @@ _SIG = {
     "ldpc_ctx_pp_row_slots": ([_vp, _vp, _vp, _vp, C.c_int, C.POINTER(C.c_int)], _i32),
     "ldpc_ctx_row_sched_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
     "ldpc_ctx_pp_inreg_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
+    "ldpc_ctx_pp_block_info": ([_vp, C.POINTER(_Cfg), _vp], _i32),
+    "ldpc_pp_block_layout": ([_i32, _i32, _vp], _i32),
     "ldpc_ctx_set_option": ([_vp, _i32, _i32], _i32),
     "ldpc_ctx_get_option": ([_vp, _i32, _pi32], _i32),
     "ldpc_nb_ctx_set_option": ([_vp, _i32, _i32], _i32),
@@ -443,9 +446,9 @@ _lib = None
 
 
 # exports added without an ABI bump: the product library has them, an older A/B build may not
-_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_redo_list", "ldpc_ctx_pp_row_slots", "ldpc_fxms_decode_batch",
-                 "ldpc_fxms_sim_launch", "ldpc_fxms_sim_batch", "ldpc_fxms_sim_trace", "ldpc_fxms_kernel_info",
-                 "ldpc_fxlms_decode_batch", "ldpc_fxlms_sim_launch", "ldpc_fxlms_sim_batch", "ldpc_fxlms_sim_trace",
+_ADDED_IN_ABI = {"ldpc_ctx_pp_inreg_info", "ldpc_ctx_pp_block_info", "ldpc_pp_block_layout", "ldpc_ctx_redo_list",
+                 "ldpc_ctx_pp_row_slots", "ldpc_fxms_decode_batch", "ldpc_fxms_sim_launch", "ldpc_fxms_sim_batch",
+                 "ldpc_fxms_sim_trace", "ldpc_fxms_kernel_info", "ldpc_fxlms_decode_batch", "ldpc_fxlms_sim_launch", "ldpc_fxlms_sim_batch", "ldpc_fxlms_sim_trace",
                  "ldpc_fxlms_kernel_info"}
 
 
@@ -479,6 +482,14 @@ def lib():
 def _check(rc: int):
     if rc != LDPC_OK:
         raise LdpcError(rc, lib().ldpc_last_error().decode(errors="replace"))
+
+
+def pp_block_layout(n_bits: int, e_pad: int) -> dict:
+    """Whether the ping-pong kernel's 768-thread block (its fixed-stride LDS layout) holds a code of
+    n_bits bits and e_pad padded edge slots, and that layout's dynamic LDS bytes. Host-only."""
+    info = np.zeros(2, dtype=np.int32)
+    _check(lib().ldpc_pp_block_layout(int(n_bits), int(e_pad), info.ctypes.data))
+    return {"fits": bool(info[0]), "launch_lds_bytes": int(info[1])}
 
 
 def device_count() -> int:
@@ -722,6 +733,12 @@ class Context:
         _check(lib().ldpc_ctx_pp_inreg_info(self._h, C.byref(cfg._c()), info.ctypes.data))
         keys = ("inreg_bits", "lds_check_edges", "bit_slot_edges", "slots_per_thread")
         return {k: int(v) for k, v in zip(keys, info)}
+
+    def pp_block_info(self, cfg: DecoderConfig) -> dict:
+        """The workgroup the ping-pong kernel launches for cfg (raises LdpcError UNSUPPORTED for other kernels)."""
+        info = np.zeros(2, dtype=np.int32)
+        _check(lib().ldpc_ctx_pp_block_info(self._h, C.byref(cfg._c()), info.ctypes.data))
+        return {"threads": int(info[0]), "launch_lds_bytes": int(info[1])}
 
     def pp_row_slots(self, cfg: DecoderConfig):
         """(cols [slots, 8] uint16, deg [slots] uint8) of the schedule the ping-pong kernel runs cfg on, from
