@@ -1574,249 +1574,230 @@ int ldpc_hwgdbf_kernel_info(ldpc_ctx *c, const ldpc_hwgdbf_cfg *cfg, char *name,
     return report_choice(ch, name, name_len, lds_bytes);
 }
 
-// ----------------------------------------------------------------- fixed-point min-sum
-static int fxms_check_cfg(const ldpc_fxms_cfg *cfg)
-{
-    return fx_check_cfg(cfg, [&] { return cfg->reserved != 0 ? set_err(LDPC_ERR_INVALID, "reserved must be 0") : LDPC_OK; });
-}
+}  // extern "C"
 
-// The kernel instance for cfg->msg_bits on the context's graph, or the refusal when one codeword's state exceeds LDS.
-static int fxms_pick(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, ldpc::FxmsChoice &ch)
-{
-    ch = ldpc::fxms_choose(c->dg, c->g->E, cfg->msg_bits);
-    if (!ch.name[0])
-        return set_err(LDPC_ERR_UNSUPPORTED,
-                       "fixed-point min-sum keeps a codeword in LDS: maxdc * M messages + 2 N = %d bytes exceed the "
-                       "bound of %d",
-                       ch.cw_bytes, ldpc::kFxmsMaxLds);
-    return LDPC_OK;
-}
+// ----------------------------------------------------------------- fixed-point min-sum, flooding and layered
+// One set of entry points over a traits type X: Cfg and Args, the cfg check, the arguments
+// beyond fx_fill, the kernel instance for the cfg on the context's graph (or the refusal when
+// one codeword's state exceeds LDS), what a launch needs first, and the launch.
+struct FxmsApi {
+    using Cfg = ldpc_fxms_cfg;
+    using Args = ldpc::FxmsArgs;
+    using Choice = ldpc::FxmsChoice;
+    static int check_cfg(const Cfg *cfg)
+    {
+        return fx_check_cfg(cfg, [&] { return cfg->reserved != 0 ? set_err(LDPC_ERR_INVALID, "reserved must be 0") : LDPC_OK; });
+    }
+    static void fill_extra(Args &, const Cfg *) {}
+    static int pick(ldpc_ctx *c, const Cfg *cfg, Choice &ch)
+    {
+        ch = ldpc::fxms_choose(c->dg, c->g->E, cfg->msg_bits);
+        if (!ch.name[0])
+            return set_err(LDPC_ERR_UNSUPPORTED,
+                           "fixed-point min-sum keeps a codeword in LDS: maxdc * M messages + 2 N = %d bytes exceed the "
+                           "bound of %d",
+                           ch.cw_bytes, ldpc::kFxmsMaxLds);
+        return LDPC_OK;
+    }
+    static int prepare(ldpc_ctx *) { return LDPC_OK; }
+    static hipError_t launch(ldpc_ctx *c, const Args &a, const Choice &ch, bool f64)
+    {
+        return ldpc::fxms_launch(c->dg, a, f64, ch, c->g->E, c->num_cus, c->stream);
+    }
+};
+
+struct FxlmsApi {
+    using Cfg = ldpc_fxlms_cfg;
+    using Args = ldpc::FxlmsArgs;
+    using Choice = ldpc::FxlmsChoice;
+    static int check_cfg(const Cfg *cfg)
+    {
+        RC_TRY(fx_check_cfg(cfg, [] { return LDPC_OK; }));
+        if (cfg->app_bits < cfg->msg_bits || cfg->app_bits > 16)
+            return set_err(LDPC_ERR_INVALID, "app_bits must be in msg_bits..16 = %d..16", cfg->msg_bits);
+        return LDPC_OK;
+    }
+    static void fill_extra(Args &a, const Cfg *cfg) { a.amax = (1 << (cfg->app_bits - 1)) - 1; }
+    // (The choice reads the graph's sizes only: no schedule, no device.)
+    static int pick(ldpc_ctx *c, const Cfg *cfg, Choice &ch)
+    {
+        ldpc::FxlmsSched sizes;
+        sizes.N = c->g->N;
+        sizes.M = c->g->M;
+        sizes.dcs = c->g->maxdc > 0 ? c->g->maxdc : 1;
+        ch = ldpc::fxlms_choose(sizes, cfg->app_bits);
+        if (!ch.name[0])
+            return set_err(LDPC_ERR_UNSUPPORTED,
+                           "layered fixed-point min-sum keeps a codeword in LDS: N APPs + the packed state of M rows = %d "
+                           "bytes exceed the bound of %d",
+                           ch.cw_bytes, ldpc::kFxlmsMaxLds);
+        return LDPC_OK;
+    }
+    // The layered row order on the device, built and uploaded by the context's first fxlms launch (after
+    // enter()), so that a context that never decodes with fxlms is created as before.
+    static int prepare(ldpc_ctx *c)
+    {
+        if (c->has_fxl) return LDPC_OK;
+        ldpc::FloodSchedule fh;
+        ldpc::LayerSchedule lh;
+        std::string err;
+        try {
+            err = ldpc::build_flood_schedule(*c->g, fh, ldpc::kMaxRowDegree);
+            if (err.empty()) err = ldpc::build_layers(*c->g, fh, lh);
+        } catch (const std::bad_alloc &) {
+            return set_err(LDPC_ERR_NOMEM, "layer schedule out of memory");
+        }
+        if (!err.empty()) return set_err(LDPC_ERR_UNSUPPORTED, "no layer schedule for this graph: %s", err.c_str());
+        HIP_TRY(upload_fxlms_sched(*c->g, lh, c->fxl_sched, c->fxl));
+        c->has_fxl = true;
+        return LDPC_OK;
+    }
+    static hipError_t launch(ldpc_ctx *c, const Args &a, const Choice &ch, bool f64)
+    {
+        return ldpc::fxlms_launch(c->fxl, a, f64, ch, c->num_cus, c->stream);
+    }
+};
 
 // Host work only (its refusals come before enter()).
-static int fxms_fill(ldpc::FxmsArgs &a, ldpc::FxmsChoice &ch, ldpc_ctx *c, const ldpc_fxms_cfg *cfg, int batch)
+template <class X>
+static int fx_setup(typename X::Args &a, typename X::Choice &ch, ldpc_ctx *c, const typename X::Cfg *cfg, int batch)
 {
     fx_fill(a, c, cfg, batch);
-    return fxms_pick(c, cfg, ch);
+    X::fill_extra(a, cfg);
+    return X::pick(c, cfg, ch);
 }
 
-static int fxms_run(ldpc_ctx *c, const ldpc::FxmsArgs &a, const ldpc::FxmsChoice &ch, bool f64)
+template <class X> static int fx_run(ldpc_ctx *c, const typename X::Args &a, const typename X::Choice &ch, bool f64)
 {
+    RC_TRY(X::prepare(c));
     RC_TRY(c->begin_launch());
-    HIP_TRY(ldpc::fxms_launch(c->dg, a, f64, ch, c->g->E, c->num_cus, c->stream));
+    HIP_TRY(X::launch(c, a, ch, f64));
     return c->end_launch();
 }
 
-int ldpc_fxms_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_fxms_cfg *cfg, const int8_t *cw,
-                           int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+template <class X>
+static int fx_decode_batch(ldpc_ctx *c, const void *y, int batch, const typename X::Cfg *cfg, const int8_t *cw, int8_t *d_out,
+                           ldpc_frame_result *frames, ldpc_counts *counts)
 {
     if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
-    RC_TRY(fxms_check_cfg(cfg));
+    RC_TRY(X::check_cfg(cfg));
     RC_TRY(check_batch(*c, batch));
-    ldpc::FxmsArgs a;
-    ldpc::FxmsChoice ch;
-    RC_TRY(fxms_fill(a, ch, c, cfg, batch));
+    typename X::Args a;
+    typename X::Choice ch;
+    RC_TRY(fx_setup<X>(a, ch, c, cfg, batch));
     RC_TRY(c->enter());
     const bool f64 = cfg->precision == LDPC_F64;
     SyncCall s(*c);
     RC_TRY(stage_given(s, c, a, f64, y, nullptr, 0, nullptr, cw));
     RC_TRY(bind_decisions(s, c, a, d_out, frames));
     RC_TRY(s.snapshot());
-    RC_TRY(fxms_run(c, a, ch, f64));
+    RC_TRY(fx_run<X>(c, a, ch, f64));
     return s.finish(counts);
 }
 
-// The refusals of the ldpc_fxms_sim_* calls that need no device, and the launch arguments of cfg.
-static int fxms_sim_setup(ldpc_ctx *c, const SimCall &q, const ldpc_fxms_cfg *cfg, ldpc::FxmsArgs &a, ldpc::FxmsChoice &ch)
+// The refusals of the sim_* calls that need no device, and the launch arguments of cfg.
+template <class X>
+static int fx_sim_setup(ldpc_ctx *c, const SimCall &q, const typename X::Cfg *cfg, typename X::Args &a, typename X::Choice &ch)
 {
-    RC_TRY(check_sim(c, [&] { return fxms_check_cfg(cfg); }, q, false));
-    RC_TRY(fxms_fill(a, ch, c, cfg, q.batch));
+    RC_TRY(check_sim(c, [&] { return X::check_cfg(cfg); }, q, false));
+    RC_TRY(fx_setup<X>(a, ch, c, cfg, q.batch));
     fill_sim(a, *c, q);
     fill_cw_table(a, *c);
     return LDPC_OK;
 }
 
-int ldpc_fxms_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
-                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+template <class X>
+static int fx_sim_launch(ldpc_ctx *c, const SimCall &q, const typename X::Cfg *cfg, ldpc_frame_result *frames_dev)
 {
-    ldpc::FxmsArgs a;
-    ldpc::FxmsChoice ch;
-    RC_TRY(fxms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
+    typename X::Args a;
+    typename X::Choice ch;
+    RC_TRY(fx_sim_setup<X>(c, q, cfg, a, ch));
     RC_TRY(require_device(frames_dev, kFramesDev));
     RC_TRY(c->enter());
     a.frame_res = (int4 *)frames_dev;
-    return fxms_run(c, a, ch, cfg->precision == LDPC_F64);
+    return fx_run<X>(c, a, ch, cfg->precision == LDPC_F64);
 }
 
+template <class X>
+static int fx_sim_trace(ldpc_ctx *c, const SimCall &q, const typename X::Cfg *cfg, void *y_out, int8_t *ycode_out,
+                        int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *accum)
+{
+    typename X::Args a;
+    typename X::Choice ch;
+    RC_TRY(fx_sim_setup<X>(c, q, cfg, a, ch));
+    RC_TRY(c->enter());
+    SyncCall s(*c);
+    RC_TRY(s.snapshot());
+    const size_t nb = (size_t)q.batch * c->g->N;
+    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), a.y_out));
+    RC_TRY(s.out(ycode_out, c->fx_code_stage, nb, a.ycode_out));
+    RC_TRY(bind_decisions(s, c, a, d_out, frames));
+    RC_TRY(fx_run<X>(c, a, ch, cfg->precision == LDPC_F64));
+    return s.finish(accum);
+}
+
+template <class X>
+static int fx_kernel_info(ldpc_ctx *c, const typename X::Cfg *cfg, char *name, int name_len, int *lds_bytes)
+{
+    RC_TRY(X::check_cfg(cfg));
+    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
+    typename X::Choice ch;
+    RC_TRY(X::pick(c, cfg, ch));
+    return report_choice(ch, name, name_len, lds_bytes);
+}
+
+extern "C" {
+
+int ldpc_fxms_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_fxms_cfg *cfg, const int8_t *cw,
+                           int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
+{
+    return fx_decode_batch<FxmsApi>(c, y, batch, cfg, cw, d_out, frames, counts);
+}
+int ldpc_fxms_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
+                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
+{
+    return fx_sim_launch<FxmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, frames_dev);
+}
 int ldpc_fxms_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
                         uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out, int8_t *d_out,
                         ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    ldpc::FxmsArgs a;
-    ldpc::FxmsChoice ch;
-    RC_TRY(fxms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
-    RC_TRY(c->enter());
-    SyncCall s(*c);
-    RC_TRY(s.snapshot());
-    const size_t nb = (size_t)batch * c->g->N;
-    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), a.y_out));
-    RC_TRY(s.out(ycode_out, c->fx_code_stage, nb, a.ycode_out));
-    RC_TRY(bind_decisions(s, c, a, d_out, frames));
-    RC_TRY(fxms_run(c, a, ch, cfg->precision == LDPC_F64));
-    return s.finish(accum);
+    return fx_sim_trace<FxmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, y_out, ycode_out, d_out, frames, accum);
 }
-
 int ldpc_fxms_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxms_cfg *cfg, uint64_t seed,
                         uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    return ldpc_fxms_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames,
-                               accum);
+    return fx_sim_trace<FxmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, nullptr, nullptr, nullptr, frames, accum);
 }
-
 int ldpc_fxms_kernel_info(ldpc_ctx *c, const ldpc_fxms_cfg *cfg, char *name, int name_len, int *lds_bytes)
 {
-    RC_TRY(fxms_check_cfg(cfg));
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    ldpc::FxmsChoice ch;
-    RC_TRY(fxms_pick(c, cfg, ch));
-    return report_choice(ch, name, name_len, lds_bytes);
-}
-
-// ----------------------------------------------------------------- layered fixed-point min-sum
-static int fxlms_check_cfg(const ldpc_fxlms_cfg *cfg)
-{
-    RC_TRY(fx_check_cfg(cfg, [] { return LDPC_OK; }));
-    if (cfg->app_bits < cfg->msg_bits || cfg->app_bits > 16)
-        return set_err(LDPC_ERR_INVALID, "app_bits must be in msg_bits..16 = %d..16", cfg->msg_bits);
-    return LDPC_OK;
-}
-
-// The kernel instance for cfg->app_bits on the context's graph, or the refusal when one codeword's state exceeds LDS.
-// (The choice reads the graph's sizes only: no schedule, no device.)
-static int fxlms_pick(ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, ldpc::FxlmsChoice &ch)
-{
-    ldpc::FxlmsSched sizes;
-    sizes.N = c->g->N;
-    sizes.M = c->g->M;
-    sizes.dcs = c->g->maxdc > 0 ? c->g->maxdc : 1;
-    ch = ldpc::fxlms_choose(sizes, cfg->app_bits);
-    if (!ch.name[0])
-        return set_err(LDPC_ERR_UNSUPPORTED,
-                       "layered fixed-point min-sum keeps a codeword in LDS: N APPs + the packed state of M rows = %d "
-                       "bytes exceed the bound of %d",
-                       ch.cw_bytes, ldpc::kFxlmsMaxLds);
-    return LDPC_OK;
-}
-
-// Host work only (its refusals come before enter()).
-static int fxlms_fill(ldpc::FxlmsArgs &a, ldpc::FxlmsChoice &ch, ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, int batch)
-{
-    fx_fill(a, c, cfg, batch);
-    a.amax = (1 << (cfg->app_bits - 1)) - 1;
-    return fxlms_pick(c, cfg, ch);
-}
-
-// The layered row order on the device, built and uploaded by the context's first fxlms launch (after
-// enter()), so that a context that never decodes with fxlms is created as before.
-static int fxlms_sched(ldpc_ctx *c)
-{
-    if (c->has_fxl) return LDPC_OK;
-    ldpc::FloodSchedule fh;
-    ldpc::LayerSchedule lh;
-    std::string err;
-    try {
-        err = ldpc::build_flood_schedule(*c->g, fh, ldpc::kMaxRowDegree);
-        if (err.empty()) err = ldpc::build_layers(*c->g, fh, lh);
-    } catch (const std::bad_alloc &) {
-        return set_err(LDPC_ERR_NOMEM, "layer schedule out of memory");
-    }
-    if (!err.empty()) return set_err(LDPC_ERR_UNSUPPORTED, "no layer schedule for this graph: %s", err.c_str());
-    HIP_TRY(upload_fxlms_sched(*c->g, lh, c->fxl_sched, c->fxl));
-    c->has_fxl = true;
-    return LDPC_OK;
-}
-
-static int fxlms_run(ldpc_ctx *c, const ldpc::FxlmsArgs &a, const ldpc::FxlmsChoice &ch, bool f64)
-{
-    RC_TRY(fxlms_sched(c));
-    RC_TRY(c->begin_launch());
-    HIP_TRY(ldpc::fxlms_launch(c->fxl, a, f64, ch, c->num_cus, c->stream));
-    return c->end_launch();
+    return fx_kernel_info<FxmsApi>(c, cfg, name, name_len, lds_bytes);
 }
 
 int ldpc_fxlms_decode_batch(ldpc_ctx *c, const void *y, int batch, const ldpc_fxlms_cfg *cfg, const int8_t *cw,
                             int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts)
 {
-    if (!c || !y) return set_err(LDPC_ERR_INVALID, "null argument");
-    RC_TRY(fxlms_check_cfg(cfg));
-    RC_TRY(check_batch(*c, batch));
-    ldpc::FxlmsArgs a;
-    ldpc::FxlmsChoice ch;
-    RC_TRY(fxlms_fill(a, ch, c, cfg, batch));
-    RC_TRY(c->enter());
-    const bool f64 = cfg->precision == LDPC_F64;
-    SyncCall s(*c);
-    RC_TRY(stage_given(s, c, a, f64, y, nullptr, 0, nullptr, cw));
-    RC_TRY(bind_decisions(s, c, a, d_out, frames));
-    RC_TRY(s.snapshot());
-    RC_TRY(fxlms_run(c, a, ch, f64));
-    return s.finish(counts);
+    return fx_decode_batch<FxlmsApi>(c, y, batch, cfg, cw, d_out, frames, counts);
 }
-
-// The refusals of the ldpc_fxlms_sim_* calls that need no device, and the launch arguments of cfg.
-static int fxlms_sim_setup(ldpc_ctx *c, const SimCall &q, const ldpc_fxlms_cfg *cfg, ldpc::FxlmsArgs &a,
-                           ldpc::FxlmsChoice &ch)
-{
-    RC_TRY(check_sim(c, [&] { return fxlms_check_cfg(cfg); }, q, false));
-    RC_TRY(fxlms_fill(a, ch, c, cfg, q.batch));
-    fill_sim(a, *c, q);
-    fill_cw_table(a, *c);
-    return LDPC_OK;
-}
-
 int ldpc_fxlms_sim_launch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
                           uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames_dev)
 {
-    ldpc::FxlmsArgs a;
-    ldpc::FxlmsChoice ch;
-    RC_TRY(fxlms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
-    RC_TRY(require_device(frames_dev, kFramesDev));
-    RC_TRY(c->enter());
-    a.frame_res = (int4 *)frames_dev;
-    return fxlms_run(c, a, ch, cfg->precision == LDPC_F64);
+    return fx_sim_launch<FxlmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, frames_dev);
 }
-
 int ldpc_fxlms_sim_trace(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
                          uint32_t stream_id, uint64_t first_cw, int batch, void *y_out, int8_t *ycode_out, int8_t *d_out,
                          ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    ldpc::FxlmsArgs a;
-    ldpc::FxlmsChoice ch;
-    RC_TRY(fxlms_sim_setup(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, a, ch));
-    RC_TRY(c->enter());
-    SyncCall s(*c);
-    RC_TRY(s.snapshot());
-    const size_t nb = (size_t)batch * c->g->N;
-    RC_TRY(s.out(y_out, c->y_stage, nb * (cfg->precision == LDPC_F64 ? 8 : 4), a.y_out));
-    RC_TRY(s.out(ycode_out, c->fx_code_stage, nb, a.ycode_out));
-    RC_TRY(bind_decisions(s, c, a, d_out, frames));
-    RC_TRY(fxlms_run(c, a, ch, cfg->precision == LDPC_F64));
-    return s.finish(accum);
+    return fx_sim_trace<FxlmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, y_out, ycode_out, d_out, frames, accum);
 }
-
 int ldpc_fxlms_sim_batch(ldpc_ctx *c, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,
                          uint32_t stream_id, uint64_t first_cw, int batch, ldpc_frame_result *frames, ldpc_counts *accum)
 {
-    return ldpc_fxlms_sim_trace(c, ebn0_db, R, cfg, seed, stream_id, first_cw, batch, nullptr, nullptr, nullptr, frames,
-                                accum);
+    return fx_sim_trace<FxlmsApi>(c, {ebn0_db, R, seed, stream_id, first_cw, batch}, cfg, nullptr, nullptr, nullptr, frames, accum);
 }
-
 int ldpc_fxlms_kernel_info(ldpc_ctx *c, const ldpc_fxlms_cfg *cfg, char *name, int name_len, int *lds_bytes)
 {
-    RC_TRY(fxlms_check_cfg(cfg));
-    if (!c) return set_err(LDPC_ERR_INVALID, "ctx is null");
-    ldpc::FxlmsChoice ch;
-    RC_TRY(fxlms_pick(c, cfg, ch));
-    return report_choice(ch, name, name_len, lds_bytes);
+    return fx_kernel_info<FxlmsApi>(c, cfg, name, name_len, lds_bytes);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // definition; no reference program computes this, its anchor is the fp64 layered decoder on
 // samples that sit on the quantiser grid).
 #pragma once
+#include "fxlms_layout.h"
 #include "fxms.h"
 
 namespace ldpc {
@@ -22,17 +23,7 @@ struct FxlmsSched {
     const uint8_t *deg = nullptr;   // [M]
 };
 
-struct FxlmsChoice {
-    const char *name = "";          // "fxlms_i8" | "fxlms_i16"; empty: the state does not fit
-    int lds_bytes = 0;              // dynamic LDS of a workgroup
-    int cw_bytes = 0;               // state bytes of one codeword
-    int threads = 0, cw_per_block = 0;
-    bool wide = false;              // int16 APPs, 15-bit magnitudes (app_bits > 8)
-    bool staged = false;            // the schedule sits in LDS beside the codewords (lds_bytes includes it)
-};
-
-constexpr int kFxlmsMaxLds = 64 * 1024;   // one codeword's state must fit (the fxms bound)
-
+// fxlms_plan of fxlms_layout.h on the schedule's sizes.
 FxlmsChoice fxlms_choose(const FxlmsSched &sc, int app_bits);
 hipError_t fxlms_launch(const FxlmsSched &sc, const FxlmsArgs &a, bool f64, const FxlmsChoice &ch, int num_cus,
                         hipStream_t s);

@@ -2,6 +2,7 @@
 // min-sum whose messages are msg_bits-wide saturating integers (no reference
 // program computes this, its anchor is fp64 min-sum on samples that sit on the quantiser grid).
 #pragma once
+#include "fxms_layout.h"
 #include "kernels.h"
 
 namespace ldpc {
@@ -29,18 +30,7 @@ struct FxmsArgs {
     unsigned *ticket;               // codewords past the first grid's are handed out by this counter
 };
 
-struct FxmsChoice {
-    const char *name = "";          // "fxms_i8" | "fxms_i16"; empty: the state does not fit
-    int lds_bytes = 0;              // dynamic LDS of a workgroup
-    int cw_bytes = 0;               // state bytes of one codeword
-    int threads = 0, cw_per_block = 0;
-    bool wide = false;              // int16 messages (msg_bits > 8)
-    bool staged = false;            // the graph sits in LDS beside the codewords (lds_bytes includes it)
-};
-
-constexpr int kFxmsMaxLds = 64 * 1024;   // one codeword's state must fit (the hwgdbf bound)
-
-// E: the graph's edges.
+// fxms_plan of fxms_layout.h on the device graph. E: the graph's edges.
 FxmsChoice fxms_choose(const DevGraph &g, int E, int msg_bits);
 hipError_t fxms_launch(const DevGraph &g, const FxmsArgs &a, bool f64, const FxmsChoice &ch, int E, int num_cus,
                        hipStream_t s);

@@ -1,6 +1,7 @@
 // hwgdbf.h -- internal launch interface of the fixed-point NGDBF hardware-model kernels
 // (hwgdbf.hip; src/NGDBFhw.cpp of the reference).
 #pragma once
+#include "hwgdbf_layout.h"
 #include "kernels.h"
 
 namespace ldpc {
@@ -31,19 +32,8 @@ struct HwgdbfArgs {
     unsigned *ticket;               // codewords past the first grid's are handed out by this counter
 };
 
-struct HwgdbfChoice {
-    const char *name = "";          // "hwgdbf_wave" | "hwgdbf_wg"; empty: the state does not fit
-    int lds_bytes = 0;              // dynamic LDS of a workgroup
-    int cw_bytes = 0;               // state bytes of one codeword
-    int threads = 0, cw_per_block = 0;
-    bool wave = false;              // a wavefront per codeword
-    bool staged = false;            // the graph sits in LDS beside the codewords (lds_bytes includes it)
-};
-
-constexpr int kHwgdbfMaxLds = 64 * 1024;   // the codewords of a workgroup; one codeword's state must fit
-
-// The shape that keeps more waves on a CU (hwgdbf.hip); option LDPC_OPT_GDBF_KERNEL = 1
-// forces the workgroup-per-codeword instance.
+// hwgdbf_plan of hwgdbf_layout.h on the device graph: the shape that keeps more waves on a CU;
+// option LDPC_OPT_GDBF_KERNEL = 1 forces the workgroup-per-codeword instance.
 // E: the graph's edges.
 HwgdbfChoice hwgdbf_choose(const DevGraph &g, int E, int qlen);
 hipError_t hwgdbf_launch(const DevGraph &g, const HwgdbfArgs &a, bool f64, const HwgdbfChoice &ch, int E, int num_cus,

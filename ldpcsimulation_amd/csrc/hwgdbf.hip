@@ -18,22 +18,20 @@
 //
 // One kernel body, two shapes (template WAVE):
 //   hwgdbf_wg    a 256-thread workgroup per codeword, two workgroup barriers per iteration
-//   hwgdbf_wave  a wavefront per codeword, up to 16 per workgroup, no workgroup barrier:
-//                a lane owns bits lane, lane + 64, ... and checks likewise; the wave's LDS
-//                operations execute in issue order, so a wavefront-scope fence (which stops
-//                the compiler from moving them) orders a phase's writes before the next reads
+//   hwgdbf_wave  the wave-per-codeword skeleton (wave_cw.h): a lane owns bits
+//                lane, lane + 64, ... and checks likewise
 // Both are persistent and take codewords by ticket: a failing frame costs maxphase * T
-// iterations, most frames a handful. State of a codeword in LDS, bytes:
-//   Y[N] (int8) | Q[qlen] (int8) | D[N] (bit 0: d, bit 1: the channel decision) | S[M] parity
-// The graph (template STAGE): where it fits beside the codewords (160 KB of LDS per
-// workgroup) every workgroup copies it into LDS once as 16-bit indices -- the checks' bits
-// slot-major (edge k of check j at k * M + j, so the lanes of a wave read consecutive
-// halfwords whatever the row degree) and the bits' checks in column order -- and the
-// iterations read no global memory but col_ptr and row_deg. Without it the 2 E indices an
-// iteration reads come from the device copy of the graph (DevGraph) through the caches.
+// iterations, most frames a handful. hwgdbf_layout.h has the state of a codeword in LDS.
+// The graph (template STAGE): where it fits beside the codewords every workgroup copies it
+// into LDS once as 16-bit indices -- the checks' bits slot-major (edge k of check j at
+// k * M + j, so the lanes of a wave read consecutive halfwords whatever the row degree) and
+// the bits' checks in column order -- and the iterations read no global memory but col_ptr
+// and row_deg. Without it the 2 E indices an iteration reads come from the device copy of
+// the graph (DevGraph) through the caches.
 #include "hwgdbf.h"
 #include "gdbf_front.h"
 #include "frame.h"
+#include "wave_cw.h"
 
 #include <hip/hip_runtime.h>
 
@@ -51,52 +49,26 @@ __device__ __forceinline__ int hw_quant(F v, F nl, F two_lmax, int nq)
 
 template <bool WAVE> __device__ __forceinline__ void grp_sync()
 {
-    if (WAVE) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    } else {
+    if (WAVE)
+        wave_sync();
+    else
         __syncthreads();
-    }
 }
 template <bool WAVE> __device__ __forceinline__ bool grp_or(int x)
 {
     if (WAVE) {
-        grp_sync<true>();
-        return __builtin_amdgcn_ballot_w64(x != 0) != 0;
+        wave_sync();
+        return wave_any(x);
     }
     return __syncthreads_or(x) != 0;
 }
 // Sum over the codeword's threads, valid in its first thread (WAVE: in every lane).
 template <bool WAVE> __device__ __forceinline__ int grp_sum(int x, int *red)
 {
-    if (WAVE) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-        return x;
-    }
+    if (WAVE) return wave_sum(x);
     int v[1] = {x};
     block_sum_n_t0<1>(v, red);
     return v[0];
-}
-
-struct HwgdbfLayout {
-    int qoff, doff, soff, total;   // of one codeword
-    int E, gcoff, cwoff;           // STAGE: edges, byte offset of the bits' checks, of the first codeword
-};
-static HwgdbfLayout hwgdbf_layout(const DevGraph &g, int E, int qlen)
-{
-    auto al = [](long long x) { return (x + 15) & ~15ll; };
-    HwgdbfLayout L;
-    const long long q = al(g.N), d = q + al(qlen), s = d + al(g.N), t = s + al(g.M);
-    L.qoff = (int)q;
-    L.doff = (int)d;
-    L.soff = (int)s;
-    L.total = t > 0x7fffffffll ? 0x7fffffff : (int)t;
-    L.E = E;
-    const long long gc = al(2ll * g.M * g.dcs), cw = gc + al(2ll * E);
-    L.gcoff = gc > 0x7fffffffll ? 0x7fffffff : (int)gc;
-    L.cwoff = cw > 0x7fffffffll ? 0x7fffffff : (int)cw;
-    return L;
 }
 
 template <typename F, int SRC, bool WAVE, bool STAGE>
@@ -128,11 +100,8 @@ __global__ __launch_bounds__(WAVE ? 1024 : 256) void k_hwgdbf(HwgdbfArgs a, DevG
     const int smult = a.smult, theta = a.theta;
     const uint32_t k0 = (uint32_t)a.seed, k1 = (uint32_t)(a.seed >> 32);
 
-    // Codewords: the grid's own first, then tickets; the first thread draws the next
-    // ticket while the current codeword decodes.
-    unsigned nxt = 0;
-    if (lane == 0) nxt = gridDim.x * upb + atomicAdd(a.ticket, 1u);
-    for (int b = blockIdx.x * upb + (WAVE ? (int)(threadIdx.x >> 6) : 0); b < a.batch;) {
+    CwTickets tk(a.ticket, a.batch, upb, lane == 0);
+    for (int b = tk.first(WAVE ? (int)(threadIdx.x >> 6) : 0); b < a.batch;) {
         const uint64_t cw = a.first_cw + (uint64_t)b;
         const int8_t *cvec = frame_codeword<SRC>(a, b, N);
         // ---- channel + front end (:218-237) ----
@@ -255,14 +224,12 @@ __global__ __launch_bounds__(WAVE ? 1024 : 256) void k_hwgdbf(HwgdbfArgs a, DevG
             if (a.iters_run) a.iters_run[b] = total;
         }
         if (WAVE) {
-            grp_sync<true>();
-            b = (int)__shfl((int)nxt, 0, 64);
-        } else {
-            if (lane == 0) red[16] = (int)nxt;
+            b = tk.next();
+        } else {   // hwgdbf_wg: the first thread hands its ticket to the workgroup
+            if (lane == 0) red[16] = (int)tk.nxt;
             __syncthreads();
-            b = red[16];   // rewritten only after the next codeword's barriers
+            b = tk.redraw(red[16]);   // rewritten only after the next codeword's barriers
         }
-        if (lane == 0 && b < a.batch) nxt = gridDim.x * upb + atomicAdd(a.ticket, 1u);
     }
 }
 
@@ -272,85 +239,28 @@ LDPC_CHECK_TU(hwgdbf)
 #error "LDPC_HWGDBF_FORCE_WAVE changes the kernel choice the tests pin: variant builds only"
 #endif
 
-// Waves a CU holds: workgroups by LDS (160 KB, each with its static words) times the waves
-// of one, up to the instances' register bound (5 waves per SIMD for the wavefront shape's
-// 84-92 VGPRs, 6 for the workgroup shape's 62-77).
-static int hwgdbf_waves_per_cu(int graph_bytes, int cw_bytes, int cw_per_block, int waves_per_block, int cap)
-{
-    const size_t wg = (size_t)graph_bytes + (size_t)cw_bytes * cw_per_block + 128;
-    if (wg > kMaxLds) return 0;
-    const int waves = (int)(kMaxLds / wg) * waves_per_block;
-    return waves < cap ? waves : cap;
-}
-
-// The default shape is the one that keeps more waves on a CU (a tie goes to the wavefront
-// shape): both are latency-bound, and the measured A/B follows the count.
 HwgdbfChoice hwgdbf_choose(const DevGraph &g, int E, int qlen)
 {
-    HwgdbfChoice ch;
-    const HwgdbfLayout L = hwgdbf_layout(g, E, qlen);
-    ch.cw_bytes = L.total;
-    if (L.total > kHwgdbfMaxLds) return ch;   // name stays empty: the caller reports the bound
-    // the 16-bit graph beside the codewords, when the indices fit 16 bits and it leaves room for a codeword
-    ch.staged = g.N <= 65535 && g.M <= 65535 && (size_t)L.cwoff + (size_t)L.total + 128 <= kMaxLds;
-    const int gb = ch.staged ? L.cwoff : 0;
-    int best_c = 1, best_w = 0;
-    for (int c = 1; c <= 16; ++c) {   // codewords (waves) per workgroup of the wavefront shape
-        const int w = hwgdbf_waves_per_cu(gb, L.total, c, c, 20);
-        if (w > best_w) {
-            best_w = w;
-            best_c = c;
-        }
-    }
-    int wg_w = hwgdbf_waves_per_cu(gb, L.total, 1, 4, 24);
 #ifdef LDPC_HWGDBF_FORCE_WAVE   // A/B builds (make hwgdbfvariant): the wavefront shape wherever it is not forced off
-    wg_w = 0;
+    const bool wg_competes = false;
+#else
+    const bool wg_competes = true;
 #endif
-    if (opt(LDPC_OPT_GDBF_KERNEL) == 1 || wg_w > best_w) {
-        ch.name = "hwgdbf_wg";
-        ch.cw_per_block = 1;
-        ch.threads = 256;
-    } else {
-        ch.name = "hwgdbf_wave";
-        ch.wave = true;
-        ch.cw_per_block = best_c;
-        ch.threads = 64 * best_c;
-    }
-    ch.lds_bytes = gb + L.total * ch.cw_per_block;
-    return ch;
-}
-
-template <typename F, int SRC, bool WAVE, bool STAGE>
-static hipError_t hwgdbf_launch_w(const DevGraph &g, const HwgdbfArgs &a, const HwgdbfChoice &ch, int E, int num_cus,
-                                  hipStream_t s)
-{
-    const HwgdbfLayout L = hwgdbf_layout(g, E, a.qlen);
-    auto fn = k_hwgdbf<F, SRC, WAVE, STAGE>;
-    int per_cu = occupancy(reinterpret_cast<const void *>(fn), ch.threads, ch.lds_bytes);   // raises the LDS limit
-    if (per_cu < 1) per_cu = 1;
-    int grid = per_cu * (num_cus > 0 ? num_cus : 1);
-    const int need = (a.batch + ch.cw_per_block - 1) / ch.cw_per_block;
-    if (grid > need) grid = need;
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(ch.threads), ch.lds_bytes, s, a, g, L);
-    return hipGetLastError();
+    return hwgdbf_plan({g.N, g.M, g.dcs, E}, qlen, opt(LDPC_OPT_GDBF_KERNEL) == 1, wg_competes);
 }
 
 hipError_t hwgdbf_launch(const DevGraph &g, const HwgdbfArgs &a, bool f64, const HwgdbfChoice &ch, int E, int num_cus,
                          hipStream_t s)
 {
-    if (a.batch <= 0) return hipSuccess;
-    if (!a.ticket || ch.cw_per_block < 1 || (size_t)ch.lds_bytes > kMaxLds) return hipErrorInvalidValue;
-    const hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned), s);
-    if (e != hipSuccess) return e;
-    return for_f_src(f64, a.src, [&](auto f, auto src) {
-        using F = typename decltype(f)::type;
-        constexpr int SRC = decltype(src)::value;
-        if (ch.staged)
-            return ch.wave ? hwgdbf_launch_w<F, SRC, true, true>(g, a, ch, E, num_cus, s)
-                           : hwgdbf_launch_w<F, SRC, false, true>(g, a, ch, E, num_cus, s);
-        return ch.wave ? hwgdbf_launch_w<F, SRC, true, false>(g, a, ch, E, num_cus, s)
-                       : hwgdbf_launch_w<F, SRC, false, false>(g, a, ch, E, num_cus, s);
-    });
+    return wave_cw_launch(
+        a, f64, ch, num_cus, s,
+        [&](auto f, auto src) {
+            using F = typename decltype(f)::type;
+            constexpr int SRC = decltype(src)::value;
+            if (ch.staged) return ch.wave ? k_hwgdbf<F, SRC, true, true> : k_hwgdbf<F, SRC, false, true>;
+            return ch.wave ? k_hwgdbf<F, SRC, true, false> : k_hwgdbf<F, SRC, false, false>;
+        },
+        g, hwgdbf_layout({g.N, g.M, g.dcs, E}, a.qlen));
 }
 
 }  // namespace ldpc
