@@ -14,7 +14,7 @@ CXXFLAGS  = -O2 -std=c++17 -ffp-contract=off -Iinclude -Wall
 LIB       = $(LIBDIR)/libldpc_hip.so
 # the min-sum kernel families that `make variant` rebuilds (one translation unit each)
 MINSUM    = kernels rows flood layered
-OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_es rows_fast rows_pp gdbf rgdbf rstat hwgdbf fxms fxlms ddbmp bp nb nb_api nb_graph api graph)
+OBJS      = $(patsubst %,$(LIBDIR)/obj/%.o,$(MINSUM) rows_es rows_fast rows_pp gdbf rgdbf rstat hwgdbf fxms fxlms fxlms_wg ddbmp bp nb nb_api nb_graph api graph)
 CLIS      = $(BINDIR)/decodeMinSum $(BINDIR)/decodeNMS $(BINDIR)/decodeNormalizedMinSum $(BINDIR)/decodeOffsetMinSum \
             $(BINDIR)/decodeMNGDBF $(BINDIR)/decodeSMNGDBF $(BINDIR)/decodeATGDBF $(BINDIR)/decodeSATGDBF $(BINDIR)/decodeSMGDBF $(BINDIR)/decodeBP \
             $(BINDIR)/decodeSGDBF $(BINDIR)/decodeMGDBF $(BINDIR)/decodeStochasticNGDBF $(BINDIR)/decodeDDBMP $(BINDIR)/decodeRSMNGDBF \
@@ -69,6 +69,7 @@ FLAGS_rstat     = $(NOSLP)
 FLAGS_hwgdbf    = $(NOSLP)
 FLAGS_fxms      = $(NOSLP)
 FLAGS_fxlms     = $(NOSLP)
+FLAGS_fxlms_wg  = $(NOSLP)
 FLAGS_ddbmp     = $(NOSLP)
 FLAGS_nb        = $(NOSLP)
 HDRS      = $(wildcard $(CSRC)/*.h) include/ldpc_hip.h

@@ -321,7 +321,8 @@ typedef enum {
                                    /* paired rows' degree-2 bits in registers (when it has pairs), 1 plain,   */
                                    /* 2 degree-aware with every bit in LDS, 3 as 0 but always on the 16-wave  */
                                    /* block (0 takes the 12-wave block where the code fits its LDS layout)    */
-    LDPC_OPT_KERNEL = 4,           /* generic kernel: 0 auto, 1 lds, 2 flood (persistent), 3 global           */
+    LDPC_OPT_KERNEL = 4,           /* generic kernel: 0 auto, 1 lds, 2 flood (persistent), 3 global; 3 also   */
+                                   /* makes ldpc_fxlms_* take the workgroup-per-codeword kernel (fxlms_wg_*)  */
     LDPC_OPT_FLOOD_MODE = 5,       /* codes beyond LDS: 0 one launch per phase, 1 the persistent kernel       */
     LDPC_OPT_FLOOD_MSG = 6,        /* phase flooding messages: 0 packed row state, 1 the c2v array            */
     LDPC_OPT_FLOOD_SPS_CHECK = 7,  /* phase flooding: resident slots per check-kernel step (0 = default)      */
@@ -691,8 +692,13 @@ int  ldpc_fxms_kernel_info(ldpc_ctx *ctx, const ldpc_fxms_cfg *cfg, char *name, 
  * LAYERED MS / OMS on grid samples bit for bit. A codeword's state -- N
  * APPs (one byte each for app_bits <= 8, else two) and the packed messages of M rows
  * (6 bytes a row, 8 with two-byte APPs, 4 more where a row has more than 26 edges) --
- * lives in LDS: a graph where it exceeds 65536 bytes is LDPC_ERR_UNSUPPORTED (DVB-S2 is
- * out of scope, as for fxms). No reference program computes this decoder. */
+ * lives in LDS: a graph where it exceeds 65536 bytes is LDPC_ERR_UNSUPPORTED (DVB-S2)
+ * unless the context's option LDPC_OPT_KERNEL is 3 ("global"). That value selects, on
+ * every graph it can hold, the kernel that gives a codeword to a workgroup, keeps the
+ * APPs in LDS and the rows' messages in global memory; it computes the same results and
+ * is LDPC_ERR_UNSUPPORTED only where N APPs plus 256 bytes exceed the 163840 bytes of
+ * LDS a workgroup may use (DVB-S2 N=64800 fits at either APP width). No reference
+ * program computes this decoder. */
 typedef struct {
     int32_t variant;     /* LDPC_MS | LDPC_NMS | LDPC_OMS; another ldpc_variant: LDPC_ERR_UNSUPPORTED */
     int32_t precision;   /* front end only */
@@ -711,8 +717,8 @@ typedef struct {
  * Monte-Carlo (the channel of frame f is the min-sum path's for the same (seed, stream_id,
  * frame); the codeword table of ldpc_sim_set_codewords applies), its synchronous form, the
  * form that also returns the samples drawn and their integer codes, and the kernel chosen
- * ("fxlms_i8": one-byte APPs and messages, app_bits <= 8; "fxlms_i16") with the LDS bytes
- * of a workgroup. The cfg is checked first, also with a NULL context. */
+ * ("fxlms_i8": one-byte APPs and messages, app_bits <= 8; "fxlms_i16"; with LDPC_OPT_KERNEL
+ * at 3 "fxlms_wg_i8" / "fxlms_wg_i16") with the LDS bytes of a workgroup. The cfg is checked first, also with a NULL context. */
 int  ldpc_fxlms_decode_batch(ldpc_ctx *ctx, const void *y, int batch, const ldpc_fxlms_cfg *cfg, const int8_t *c,
                              int8_t *d_out, ldpc_frame_result *frames, ldpc_counts *counts);
 int  ldpc_fxlms_sim_launch(ldpc_ctx *ctx, double ebn0_db, double R, const ldpc_fxlms_cfg *cfg, uint64_t seed,

@@ -48,7 +48,8 @@ static const char *check_site_name(unsigned s)
         "rgdbf_rows bit flag", "rgdbf_rows check parity", "hwgdbf decision byte", "hwgdbf check parity",
         "hwgdbf noise sample", "rstat decision byte", "rstat check parity", "rows_es gather (app entry)",
         "rows_es scatter (c2v slot)", "rows_es bit read (c2v slot)", "rows_es app write", "fxms message slot",
-        "fxms decision byte", "fxlms schedule entry", "fxlms APP", "fxlms row state"};
+        "fxms decision byte", "fxlms schedule entry", "fxlms APP", "fxlms row state",
+        "fxlms_wg schedule entry", "fxlms_wg APP", "fxlms_wg row state", "fxlms_wg global slot"};
     return s < CHK_SITES ? names[s] : "?";
 }
 long check_collect(hipStream_t s, char *msg, size_t msg_len)
@@ -58,7 +59,7 @@ long check_collect(hipStream_t s, char *msg, size_t msg_len)
     hipError_t (*const take[])(CheckRec *) = {check_take_rows_pp, check_take_rows_fast, check_take_flood, check_take_layered,
                                               check_take_gdbf, check_take_nb, check_take_bp, check_take_ddbmp,
                                               check_take_rgdbf, check_take_hwgdbf, check_take_rstat, check_take_rows_es,
-                                              check_take_fxms, check_take_fxlms};
+                                              check_take_fxms, check_take_fxlms, check_take_fxlms_wg};
     long total = 0;
     for (auto fn : take) {
         CheckRec r{};
@@ -83,6 +84,7 @@ struct ldpc_ctx : CtxCore {
     bool has_fxl = false;                                 // layered fixed-point min-sum: the layered row order, built by its first launch
     ldpc::FxlmsSched fxl{};
     DevBuf fxl_sched;
+    int fxl_wg_grid = 0;                                  // fxlms_wg: the workgroups of the launch being made (its slots are in gscratch)
     int cw_rows = 0;
     ldpc::AuxStream aux;          // second stream of the flooding phase launches (kernels.h)
     bool has_rs = false;
@@ -1599,7 +1601,7 @@ struct FxmsApi {
                            ch.cw_bytes, ldpc::kFxmsMaxLds);
         return LDPC_OK;
     }
-    static int prepare(ldpc_ctx *) { return LDPC_OK; }
+    static int prepare(ldpc_ctx *, const Args &, const Choice &, bool) { return LDPC_OK; }
     static hipError_t launch(ldpc_ctx *c, const Args &a, const Choice &ch, bool f64)
     {
         return ldpc::fxms_launch(c->dg, a, f64, ch, c->g->E, c->num_cus, c->stream);
@@ -1618,24 +1620,44 @@ struct FxlmsApi {
         return LDPC_OK;
     }
     static void fill_extra(Args &a, const Cfg *cfg) { a.amax = (1 << (cfg->app_bits - 1)) - 1; }
-    // (The choice reads the graph's sizes only: no schedule, no device.)
+    // (The choice reads the graph's sizes only: no schedule, no device.) LDPC_OPT_KERNEL = 3
+    // ("global") takes the workgroup kernel, whose row state is in global memory (fxlms_wg.hip).
     static int pick(ldpc_ctx *c, const Cfg *cfg, Choice &ch)
     {
         ldpc::FxlmsSched sizes;
         sizes.N = c->g->N;
         sizes.M = c->g->M;
         sizes.dcs = c->g->maxdc > 0 ? c->g->maxdc : 1;
+        if (c->opts.v[LDPC_OPT_KERNEL] == 3) {
+            ch = ldpc::fxlms_wg_choose(sizes, cfg->app_bits);
+            if (!ch.name[0])
+                return set_err(LDPC_ERR_UNSUPPORTED,
+                               "layered fixed-point min-sum with LDPC_OPT_KERNEL = 3 keeps a codeword's APPs in LDS: N APPs + "
+                               "%d bytes of scratch = %d bytes exceed the bound of %d",
+                               ldpc::kFxlmsWgRed, ch.cw_bytes, (int)ldpc::kWaveCwLds);
+            return LDPC_OK;
+        }
         ch = ldpc::fxlms_choose(sizes, cfg->app_bits);
         if (!ch.name[0])
             return set_err(LDPC_ERR_UNSUPPORTED,
                            "layered fixed-point min-sum keeps a codeword in LDS: N APPs + the packed state of M rows = %d "
-                           "bytes exceed the bound of %d",
+                           "bytes exceed the bound of %d; LDPC_OPT_KERNEL = 3 (global) selects the kernel that keeps the "
+                           "rows' state in global memory",
                            ch.cw_bytes, ldpc::kFxlmsMaxLds);
         return LDPC_OK;
     }
     // The layered row order on the device, built and uploaded by the context's first fxlms launch (after
     // enter()), so that a context that never decodes with fxlms is created as before.
-    static int prepare(ldpc_ctx *c)
+    // The workgroup kernel's global slots, one per workgroup of this launch, grow with the grid.
+    static int prepare(ldpc_ctx *c, const Args &a, const Choice &ch, bool f64)
+    {
+        RC_TRY(prepare_sched(c));
+        if (!ch.wg) return LDPC_OK;
+        c->fxl_wg_grid = ldpc::fxlms_wg_grid(a, f64, ch, c->num_cus);
+        HIP_TRY(c->gscratch.ensure((size_t)ch.slot_bytes * (size_t)c->fxl_wg_grid));
+        return LDPC_OK;
+    }
+    static int prepare_sched(ldpc_ctx *c)
     {
         if (c->has_fxl) return LDPC_OK;
         ldpc::FloodSchedule fh;
@@ -1654,6 +1676,7 @@ struct FxlmsApi {
     }
     static hipError_t launch(ldpc_ctx *c, const Args &a, const Choice &ch, bool f64)
     {
+        if (ch.wg) return ldpc::fxlms_wg_launch(c->fxl, a, f64, ch, c->gscratch.p, c->fxl_wg_grid, c->stream);
         return ldpc::fxlms_launch(c->fxl, a, f64, ch, c->num_cus, c->stream);
     }
 };
@@ -1669,7 +1692,7 @@ static int fx_setup(typename X::Args &a, typename X::Choice &ch, ldpc_ctx *c, co
 
 template <class X> static int fx_run(ldpc_ctx *c, const typename X::Args &a, const typename X::Choice &ch, bool f64)
 {
-    RC_TRY(X::prepare(c));
+    RC_TRY(X::prepare(c, a, ch, f64));
     RC_TRY(c->begin_launch());
     HIP_TRY(X::launch(c, a, ch, f64));
     return c->end_launch();

@@ -54,6 +54,10 @@ enum CheckSite : unsigned {
     CHK_FXLMS_SCHED,       // fxlms: schedule entry of a row's edge         (< maxdc * M)
     CHK_FXLMS_BIT,         // fxlms: APP a row gathers / scatters           (< N)
     CHK_FXLMS_ROW,         // fxlms: packed state of a layer's row          (< M)
+    CHK_FXLMS_WG_SCHED,    // fxlms_wg: schedule entry of a row's edge      (< maxdc * M)
+    CHK_FXLMS_WG_BIT,      // fxlms_wg: APP a row gathers / scatters        (< N)
+    CHK_FXLMS_WG_ROW,      // fxlms_wg: layered position of a layer's row, the index of its state words (< M)
+    CHK_FXLMS_WG_SLOT,     // fxlms_wg: global slot of the workgroup         (< slots allocated)
     CHK_SITES
 };
 
@@ -121,6 +125,7 @@ hipError_t check_take_rstat(CheckRec *out);
 hipError_t check_take_rows_es(CheckRec *out);
 hipError_t check_take_fxms(CheckRec *out);
 hipError_t check_take_fxlms(CheckRec *out);
+hipError_t check_take_fxlms_wg(CheckRec *out);
 #endif
 
 }  // namespace ldpc

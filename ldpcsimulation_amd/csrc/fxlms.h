@@ -1,4 +1,6 @@
-// fxlms.h -- internal launch interface of the layered fixed-point min-sum kernel (fxlms.hip):
+// fxlms.h -- internal launch interface of the layered fixed-point min-sum kernels (fxlms.hip: a
+// wavefront per codeword, its state in LDS; fxlms_wg.hip: a workgroup per codeword, the APPs in
+// LDS and the row state in a global slot, for codes beyond the first's 64 KiB):
 // row-layered MS / NMS / OMS with a saturating app_bits-wide posterior per bit and a
 // msg_bits-wide message per edge (include/ldpc_hip.h ldpc_fxlms_cfg has the
 // definition; no reference program computes this, its anchor is the fp64 layered decoder on
@@ -27,5 +29,13 @@ struct FxlmsSched {
 FxlmsChoice fxlms_choose(const FxlmsSched &sc, int app_bits);
 hipError_t fxlms_launch(const FxlmsSched &sc, const FxlmsArgs &a, bool f64, const FxlmsChoice &ch, int num_cus,
                         hipStream_t s);
+
+// fxlms_wg.hip. fxlms_wg_plan of fxlms_layout.h on the schedule's sizes; the workgroups of a
+// launch (what the CUs hold, no more than the batch), each of which needs ch.slot_bytes of
+// `scratch`; and the launch over `grid` workgroups.
+FxlmsChoice fxlms_wg_choose(const FxlmsSched &sc, int app_bits);
+int fxlms_wg_grid(const FxlmsArgs &a, bool f64, const FxlmsChoice &ch, int num_cus);
+hipError_t fxlms_wg_launch(const FxlmsSched &sc, const FxlmsArgs &a, bool f64, const FxlmsChoice &ch, void *scratch, int grid,
+                           hipStream_t s);
 
 }  // namespace ldpc

@@ -35,6 +35,9 @@ line for each point.
     # its row-layered form: saturating posteriors of --app-bits bits (default msg-bits + 1), rows in the graph's layer order
     python -m ldpcsimulation_amd.sweep ALIST --rate 0.5 --snr 1.5 2.0 -T 25 --fxlms --variant nms --scale 3 2 \\
         --quantize 1.9375 5 --msg-bits 8 --app-bits 9 --early-stop
+    # ... on a code beyond 64 KiB of state (DVB-S2 N=64800): the workgroup-per-codeword kernel, same results
+    python -m ldpcsimulation_amd.sweep dvbs2_1_2.alist --rate 0.5 --snr 1.2 1.4 -T 25 --fxlms --fx-kernel wg --variant nms \\
+        --scale 3 2 --msg-bits 8 --app-bits 9 --early-stop
 Log line: SNR BER avgIt FER T [Ymax] [alpha] [delta] alist (--fxms: SNR BER avgIt FER T Ymax Q msgBits [num shift] [beta] alist; --fxlms: SNR BER avgIt FER T Ymax Q msgBits appBits [num shift] [beta] alist; DD-BMP: SNR BER avgIt FER T Ymax Q alist; EMS: SNR BER avgIt FER T nm offset alist;
 BER over coded bits, 4 per GF(16) symbol; --gdbf: SNR BER avgIt FER T theta noiseScale lambda alpha windowsize Ymax
 [maxphase] alist, maxphase with RSMNGDBF only -- the reference's own GDBF log lines are the CLIs' job;
@@ -114,6 +117,9 @@ def parse(argv=None):
                    help="layered fixed-point min-sum (saturating posteriors, integer messages, the graph's layer order): "
                         "the settings of --fxms and --app-bits")
     p.add_argument("--app-bits", type=int, help="--fxlms: posterior width in bits, msg-bits..16 (default msg-bits + 1)")
+    p.add_argument("--fx-kernel", choices=["auto", "wg"], default="auto",
+                   help="--fxlms: wg forces the workgroup-per-codeword kernel (option kernel = global), which also holds "
+                        "codes beyond 64 KiB of state such as DVB-S2 N=64800; the results do not depend on the kernel")
     p.add_argument("--msg-bits", type=int, help="--fxms / --fxlms: message width in bits, 2..16 (default 6)")
     p.add_argument("--scale", type=int, nargs=2, metavar=("NUM", "SHIFT"),
                    help="--fxms --variant nms: magnitudes become (m * NUM) >> SHIFT (default 3 2)")
@@ -164,6 +170,8 @@ def parse(argv=None):
                 p.error("--" + n.replace("_", "-") + " belongs to --fxms / --fxlms")
     if a.app_bits is not None and not a.fxlms:
         p.error("--app-bits belongs to --fxlms")
+    if a.fx_kernel != "auto" and not a.fxlms:
+        p.error("--fx-kernel belongs to --fxlms")
     gdbf_only = [n for n in ("theta", "lam", "noise_scale", "window", "nq", "maxphase") if getattr(a, n) is not None]
     if a.hwgdbf:
         if a.gdbf or a.ems or a.schedule != "flooding" or a.variant != "ms":
@@ -463,6 +471,8 @@ def _fxms_sweep(a, seed, world, rank, device, ck=None) -> int:
     g = native.Graph.from_alist(a.alist)
     ctx = native.Context(g, device, a.batch)
     layered = bool(getattr(a, "fxlms", False))
+    if getattr(a, "fx_kernel", "auto") == "wg":   # the same results from another kernel: no checkpoint setting
+        ctx.set_option("kernel", "global")
     s = _fxlms_settings(a) if layered else _fxms_settings(a)
     cfg = (native.FxlmsConfig if layered else native.FxmsConfig)(
         variant=VARIANTS[a.variant], T=a.iterations, early_stop=bool(a.early_stop),

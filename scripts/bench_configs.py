@@ -43,7 +43,10 @@ src/newstat.cpp:305-429 (the rstat_* lines: 200 frames x 100 attempts as scripts
 runs them; *_wg forces the workgroup-per-attempt kernel). The fxms_* lines (fixed-point min-sum,
 fxms.hip) have no reference counterpart; nms_1944_* is the floating-point NMS beside them. The
 fxlms_* lines are its row-layered form (fxlms.hip) at app_bits = msg_bits + 1, written to
-profiles/fxlms_configs.jsonl beside the fxms_* lines of the same session.
+profiles/fxlms_configs.jsonl beside the fxms_* lines of the same session. The fxlms_wg_* lines
+force its workgroup-per-codeword kernel (fxlms_wg.hip, option kernel = global): DVB-S2 N=64800,
+which only that kernel holds, at two-byte and at one-byte APPs, and N=1944 beside fxlms_1944_nms_m8;
+they are written to profiles/fxlms_wg_configs.jsonl.
 """
 import argparse
 import csv
@@ -143,6 +146,17 @@ for _snr, _es, _tag in ((1.5, False, ""), (3.0, True, "_es")):
             kind="fxlms", code="80211n_1944_r12.alist", prec="f32", T=50, batch=65536, snr=_snr, msg_bits=_bits,
             early_stop=_es, what=f"layered fixed-point NMS 3/4 on 802.11n N=1944, msg_bits {_bits}, app_bits {_bits + 1}, "
                                  f"Q 5, T{'<=' if _es else '='}50")
+    # the workgroup-per-codeword kernel: DVB-S2 at 8/9 bits (two-byte APPs) and 8/8 (one-byte) -- 8,192 frames, 16 or
+    # 32 for each resident workgroup, at config 3's 1.0 dB and with early stop at 1.4 dB -- and N=1944 at 8/9
+    _dsnr = 1.4 if _es else 1.0
+    for _name, _code, _app, _batch, _wsnr in (("dvbs2_nms_m8", "dvbs2_1_2.alist", 9, 8192, _dsnr),
+                                              ("dvbs2_nms_m8a8", "dvbs2_1_2.alist", 8, 8192, _dsnr),
+                                              ("1944_nms_m8", "80211n_1944_r12.alist", 9, 65536, _snr)):
+        CONFIGS[f"fxlms_wg_{_name}{_tag}"] = dict(
+            kind="fxlms", code=_code, prec="f32", T=50, batch=_batch, snr=_wsnr, msg_bits=8, app_bits=_app,
+            early_stop=_es, kernel="global",
+            what=f"layered fixed-point NMS 3/4 on {_code.split('.')[0]}, msg_bits 8, app_bits {_app}, Q 5, "
+                 f"T{'<=' if _es else '='}50, fxlms_wg forced")
     for _prec in ("f32", "f64"):
         CONFIGS[f"nms_1944_{_prec}{_tag}"] = dict(
             kind="minsum", code="80211n_1944_r12.alist", variant="nms", prec=_prec, T=50, batch=65536, snr=_snr,
@@ -238,8 +252,10 @@ class Workload:
             info = self.ctx.fxms_kernel_info(self.cfg)
             self.kernel, self.lds_bytes = info["kernel"], info["lds_bytes"]
         elif c["kind"] == "fxlms":
+            if c.get("kernel"):
+                self.ctx.set_option("kernel", c["kernel"])
             self.cfg = native.FxlmsConfig(variant=native.NMS, T=c["T"], qbits=5, msg_bits=c["msg_bits"],
-                                          app_bits=c["msg_bits"] + 1, nms_num=3, nms_shift=2, early_stop=c["early_stop"],
+                                          app_bits=c.get("app_bits", c["msg_bits"] + 1), nms_num=3, nms_shift=2, early_stop=c["early_stop"],
                                           ymax=31 / 16, precision=prec)
             self.launch_fn = self.ctx.fxlms_sim_launch
             info = self.ctx.fxlms_kernel_info(self.cfg)
