@@ -339,7 +339,7 @@ typedef enum {
     LDPC_OPT_FAST_BPC = 17,        /* rows_fast: blocks per CU cap (0 = occupancy)                            */
     LDPC_OPT_BP_KERNEL = 18,       /* belief propagation: 0 bp_rows when the code fits, 1 the generic kernel  */
     LDPC_OPT_GDBF_KERNEL = 19,     /* GDBF: 0 gdbf_rows when the code and flags fit, 1 the generic kernel     */
-    LDPC_OPT_EMS_THREADS = 20,     /* EMS (nb context), row degree 4: 0 = 1024 threads, 512                   */
+    LDPC_OPT_EMS_THREADS = 20,     /* EMS (nb context), row degree 4 (q < 16: any): 0 = 1024 threads, 512     */
     LDPC_OPT_EMS_SWIZZLE = 21,     /* EMS (nb context): 0 swizzled message slots, 1 the plain layout          */
     LDPC_OPT_DDBMP_KERNEL = 22     /* DD-BMP: 0 ddbmp_rows when the code fits, 1 the generic kernel           */
 } ldpc_option;
@@ -739,7 +739,11 @@ int  ldpc_fxlms_kernel_info(ldpc_ctx *ctx, const ldpc_fxlms_cfg *cfg, char *name
  * messages. Channel: each symbol is m = log2(q) BPSK bits (bit i of the
  * symbol's integer value, 0 -> +1), y = x(1 + sigma n), bit LLR 4y/N0.
  * Exact definition: DESIGN.md §11 and oracle/ems_oracle.c. No reference
- * counterpart computes this (parity unpinned); q = 2 reduces to min-sum. */
+ * counterpart computes this (parity unpinned); q = 2 reduces to min-sum.
+ * Graphs take q = 2..64; the device kernels decode q = 4, 8 and 16 (the
+ * reference's GF(4) and GF(8) codes among them). On-device noise: symbol v
+ * makes one Philox call (counter word 0 = v) and its first m normals are the
+ * symbol's bits 0..m-1. */
 typedef struct ldpc_nb_graph ldpc_nb_graph;
 typedef struct ldpc_nb_ctx ldpc_nb_ctx;
 
@@ -767,13 +771,18 @@ int  ldpc_nb_graph_load_alist(const char *path, ldpc_nb_graph **out);
 int  ldpc_nb_graph_info(const ldpc_nb_graph *g, int *N, int *M, int *q, int *E, int *maxdv, int *maxdc);
 void ldpc_nb_graph_destroy(ldpc_nb_graph *g);
 
-/* Device context (GF(16), row degree <= 8). */
+/* Device context: q in {4, 8, 16}, row degree <= 8, N <= 65535, maxdc * M <=
+ * 65535, and the bit LLRs, decisions and syndrome of one codeword within LDS.
+ * LDPC_ERR_UNSUPPORTED otherwise: q = 2 (binary codes have their own
+ * decoders) and q = 32, 64 (a check lane cannot hold their vectors). */
 int  ldpc_nb_ctx_create(int device, const ldpc_nb_graph *g, int max_batch, ldpc_nb_ctx **out);
 int  ldpc_nb_ctx_set_stream(ldpc_nb_ctx *ctx, void *hip_stream);
 void ldpc_nb_ctx_destroy(ldpc_nb_ctx *ctx);
 int  ldpc_nb_ctx_read_counts(ldpc_nb_ctx *ctx, ldpc_nb_counts *out, int reset);
 int  ldpc_nb_ctx_last_kernel_ms(ldpc_nb_ctx *ctx, float *ms);
-/* "ems_lds" (messages in LDS) or "ems_global" (a global slot per workgroup). */
+/* "ems_lds" (messages in LDS), "ems_global" (a global slot per workgroup) or
+ * "ems_global_sched" (that, and the schedule tables read from global memory:
+ * codes whose tables exceed LDS, such as the reference's GF(4) code). */
 int  ldpc_ems_kernel_info(ldpc_nb_ctx *ctx, char *name, int name_len, int *lds_bytes);
 /* (ABI 10) The EMS options of ldpc_option (LDPC_OPT_EMS_*); the others are refused. */
 int  ldpc_nb_ctx_set_option(ldpc_nb_ctx *ctx, int option, int value);

@@ -22,6 +22,14 @@ struct NbDevGraph {
     const uint8_t *gf_inv;        // [q]
 };
 
+// The schedule as k_ems packs it, in device memory for the instance that does not stage
+// it in LDS (ems_global_sched); vh is NbDevGraph::col_h.
+struct NbDevSched {
+    const uint8_t *cn_d;          // [M]  check degree
+    const uint32_t *vn;           // [N]  first column entry << 8 | degree
+    const uint16_t *vslot;        // [E]  position-major slots, nlist order
+};
+
 struct NbArgs {
     int batch, T, nm, early_stop, src;
     float offset, n0, sigma;
@@ -39,16 +47,17 @@ struct NbArgs {
 
 struct NbChoice {
     bool ok = false;              // false: no kernel decodes the graph (degree, LDS schedule or 16-bit indices)
-    const char *name = "";        // "ems_lds" | "ems_global"
+    const char *name = "";        // "ems_lds" | "ems_global" | "ems_global_sched"
     int lds_bytes = 0, threads = 0, dc = 0;
-    size_t slot_bytes = 0;        // ems_global: message bytes per resident codeword
+    size_t slot_bytes = 0;        // ems_global*: message bytes per resident codeword
+    bool sched_lds = true;        // false (ems_global_sched): the schedule tables stay in global memory
 };
 
 // the chunk stride of a device graph's message layout (nb_layout.h)
 __host__ __device__ inline int nb_ep(const NbDevGraph &g) { return nb_ep(g.maxdc, g.M); }
 
 NbChoice nb_choose(const NbDevGraph &g, int maxdc);
-hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, void *scratch, int slots,
-                     int num_cus, hipStream_t s);
+hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, const NbDevSched &ds, void *scratch,
+                     int slots, int num_cus, hipStream_t s);
 
 }  // namespace ldpc

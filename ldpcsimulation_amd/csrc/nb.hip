@@ -1,10 +1,11 @@
-// nb.hip -- CDNA4 (gfx950) kernels of the non-binary GF(16) Extended Min-Sum
-// decoder (BASELINE config 5; no reference counterpart:
+// nb.hip -- CDNA4 (gfx950) kernels of the non-binary Extended Min-Sum decoder
+// over GF(4), GF(8) and GF(16) (BASELINE config 5; no reference counterpart:
 // the reference's NB model, SystemC/NB-LDPC/inc/nodes.h, is a q^dc-LUT BP
 // that does not compile). The algorithm is defined by the CPU oracle
 // oracle/ems_oracle.c, which this reproduces bit for bit.
 //
-// Mapping: every node works on whole 16-entry message vectors held in the
+// Mapping (written for Q = 16; Q = 4 and 8 are the same code on shorter vectors): every
+// node works on whole Q-entry message vectors held in the
 // registers of ONE lane, so no cross-lane traffic is needed.
 //   check node: one lane per (check, direction); the elementary check node
 //     W(x) = min_a P(a) + R(a ^ x) is 256 register adds and mins, and the two
@@ -18,7 +19,8 @@
 // codeword at a time (persistent over the batch); its edge messages (16 fp32
 // per edge, in place: c2v after the check phase, v2c after the symbol phase)
 // and bit LLRs live in LDS when they fit (128 KB of messages for N = 1000,
-// E = 2000), else in a global slot per workgroup.
+// E = 2000), else in a global slot per workgroup; where even the schedule tables do
+// not fit beside the bit LLRs, they are read from their device copy (SCHED_LDS = false).
 #include "nb.h"
 #include "device_common.h"
 #include "kernels.h"
@@ -31,6 +33,9 @@
 namespace ldpc {
 
 constexpr float kInf = __builtin_huge_valf();
+// Threads per workgroup of the GF(4) and GF(8) instances unless LDPC_OPT_EMS_THREADS says
+// otherwise (512 against 1024 on both reference codes and a small one).
+constexpr int kNbThreadsSmallQ = 1024;
 
 // Check-lane addresses recomputed per iteration (1) or hoisted by the compiler (0).
 #ifndef LDPC_EMS_OPAQUE
@@ -107,8 +112,11 @@ struct NbSched {
 
 typedef __attribute__((address_space(3))) float LdsF;
 
-// GF(16) (x^4 + x + 1): v * x.
-__device__ __forceinline__ int gf16_xt(int v) { return ((v << 1) & 15) ^ ((v & 8) ? 3 : 0); }
+// v * x in GF(4) (x^2 + x + 1), GF(8) (x^3 + x + 1) and GF(16) (x^4 + x + 1): in all
+// three the top power reduces to x + 1.
+template <int Q>
+__device__ __forceinline__ int gf_xt(int v) { return ((v << 1) & (Q - 1)) ^ ((v & (Q >> 1)) ? 3 : 0); }
+template <int Q> constexpr int kBitsOf = Q == 16 ? 4 : Q == 8 ? 3 : 2;
 
 // ---- check node: one lane per (check, direction), the message vectors in registers ----
 template <int Q>
@@ -262,20 +270,24 @@ __device__ __forceinline__ void cn_lane(float *msg, int Ep, int M, int j, int di
 // This symbol's share of the parity checks of the new decisions: h * dec xor-ed
 // into its checks' syndrome bytes (slot = k*M + j: check j = slot mod M, k < DC).
 // GF(16) sums are xors, so the order of the atomics does not matter.
-template <int DC>
+template <int Q, int DC>
 __device__ __forceinline__ void syndrome_edge(int M, int s, int hv, int d, uint32_t *synd)
 {
     int j = LDPC_CHK(s, M * DC, CHK_EMS_SLOT);
 #pragma unroll
     for (int k = 1; k < DC; ++k) j -= j >= M ? M : 0;
-    const int h1 = hv & 15, h2 = gf16_xt(h1), h4 = gf16_xt(h2), h8 = gf16_xt(h4);
-    const int hd = ((d & 1) ? h1 : 0) ^ ((d & 2) ? h2 : 0) ^ ((d & 4) ? h4 : 0) ^ ((d & 8) ? h8 : 0);
+    int hp = hv & 15, hd = 0;   // hp = h * 2^i
+#pragma unroll
+    for (int i = 0; i < kBitsOf<Q>; ++i) {
+        hd ^= ((d >> i) & 1) ? hp : 0;
+        hp = gf_xt<Q>(hp);
+    }
     if (hd) atomicXor(&synd[j >> 2], (uint32_t)hd << (8 * (j & 3)));
 }
-template <int DC>
+template <int Q, int DC>
 __device__ __forceinline__ void vn_syndrome(const NbSched &sc, int e0, int e1, int d, uint32_t *synd)
 {
-    for (int e = e0; e < e1; ++e) syndrome_edge<DC>(sc.M, sc.vslot[e], sc.vh[e], d, synd);
+    for (int e = e0; e < e1; ++e) syndrome_edge<Q, DC>(sc.M, sc.vslot[e], sc.vh[e], d, synd);
 }
 
 // After the symbol phase's barrier: any check unsatisfied? Every syndrome word is
@@ -323,9 +335,13 @@ struct MsgAddr {
     __device__ void edge(int s, int hv, int (&ad)[Q]) const
     {
         s = LDPC_CHK(s, 1 << (sh - 4), CHK_EMS_SLOT);   // slots [0, Ep)
-        const int h1 = hv & 15, f = hv >> 4;
-        const int h2 = gf16_xt(h1), h4 = gf16_xt(h2), h8 = gf16_xt(h4);
-        const int L[4] = {lam(h1), lam(h2), lam(h4), lam(h8)};
+        const int f = hv >> 4;
+        int L[kBitsOf<Q>], hp = hv & 15;   // lambda(h * 2^i)
+#pragma unroll
+        for (int i = 0; i < kBitsOf<Q>; ++i) {
+            L[i] = lam(hp);
+            hp = gf_xt<Q>(hp);
+        }
         ad[0] = xbase ^ (s << 4) ^ lam(f);
 #pragma unroll
         for (int a = 1; a < Q; ++a) ad[a] = ad[a & (a - 1)] ^ L[__builtin_ctz(a)];
@@ -348,7 +364,7 @@ struct MsgAddr {
 // (ems_codeword), so the symbol phase starts without two dependent LDS round trips.
 template <int Q, int K>
 struct VnPre {
-    float lv[4];            // the symbol's bit LLRs
+    float lv[kBitsOf<Q>];   // the symbol's bit LLRs
     int e0, e1;
     int sk[K], hk[K];
 };
@@ -357,12 +373,17 @@ template <int Q, int MB, int VD, bool GS>
 __device__ __forceinline__ void vn_pre(const MsgAddr<Q, GS> &ma, int v, const NbSched &sc, const float *lam,
                                        VnPre<Q, (VD > 0 ? VD : 1)> &p)
 {
-    static_assert(Q == 16 && MB == 4, "GF(16)");
-    const float4 l4 = *reinterpret_cast<const float4 *>(lam + v * MB);
-    p.lv[0] = l4.x;
-    p.lv[1] = l4.y;
-    p.lv[2] = l4.z;
-    p.lv[3] = l4.w;
+    static_assert(MB == kBitsOf<Q>, "one LLR per bit of a symbol");
+    if constexpr (MB == 4) {
+        const float4 l4 = *reinterpret_cast<const float4 *>(lam + v * MB);
+        p.lv[0] = l4.x;
+        p.lv[1] = l4.y;
+        p.lv[2] = l4.z;
+        p.lv[3] = l4.w;
+    } else {
+#pragma unroll
+        for (int i = 0; i < MB; ++i) p.lv[i] = lam[v * MB + i];
+    }
     const uint32_t vp = sc.vn[v];
     p.e0 = vp >> 8;
     p.e1 = p.e0 + (vp & 255);
@@ -432,7 +453,7 @@ __device__ __forceinline__ void vn_post(const MsgAddr<Q, GS> &ma, int v, const N
         dec[v] = (uint8_t)best;
 #pragma unroll
         for (int k = 0; k < K; ++k)
-            if (k < deg) syndrome_edge<DC>(sc.M, p.sk[k], p.hk[k], best, synd);
+            if (k < deg) syndrome_edge<Q, DC>(sc.M, p.sk[k], p.hk[k], best, synd);
 #pragma unroll
         for (int k = 0; k < K; ++k)
             if (k < deg) {
@@ -462,7 +483,7 @@ __device__ __forceinline__ void vn_post(const MsgAddr<Q, GS> &ma, int v, const N
             best = a;
         }
     dec[v] = (uint8_t)best;
-    vn_syndrome<DC>(sc, e0, e1, best, synd);
+    vn_syndrome<Q, DC>(sc, e0, e1, best, synd);
     if (init) return;
     for (int e = e0; e < e1; ++e) {
         ma.edge(sc.vslot[e], sc.vh[e], ad);
@@ -508,12 +529,12 @@ __device__ __forceinline__ void ems_codeword(const NbArgs &a, const NbDevGraph &
 #pragma unroll
                 for (int i = 0; i < MB; ++i) yv[i] = a.y[((size_t)b * N + v) * MB + i];
             } else {
-                static_assert(MB == 4, "one Philox call per GF(16) symbol");
+                static_assert(MB <= 4, "one Philox call per symbol: its first MB normals");
                 uint32_t u[4];
                 philox4x32_10((uint32_t)v, (uint32_t)cw, (uint32_t)(cw >> 32), a.stream_id, k0, k1, u);
                 float n[4];
                 box_muller(u[0], u[1], n[0], n[1]);
-                box_muller(u[2], u[3], n[2], n[3]);
+                if (MB > 2) box_muller(u[2], u[3], n[2], n[3]);
 #pragma unroll
                 for (int i = 0; i < MB; ++i) {
                     const float xb = ((cs >> i) & 1) ? -1.0f : 1.0f;
@@ -667,24 +688,18 @@ __device__ __forceinline__ void ems_codeword(const NbArgs &a, const NbDevGraph &
 #endif
 }
 
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-
-// dynamic LDS: [msg 16*Ep f32 (ems_lds only)] [lam N*m f32] [dec N u8] [cn_d M u8]
+// dynamic LDS: [msg Q*Ep f32 (ems_lds only)] [lam N*m f32] [dec N u8] [cn_d M u8]
 //              [vn N u32] [vslot E u16] [vh E u8] [synd ceil(M/4) u32] [red 48 i32] [flags 16 i32]
 // (no static LDS: the messages start at LDS address 0, so the symbol node's XOR-formed
-// offsets are its ds addresses as they are, without an add per entry)
-__host__ __device__ inline size_t aux_bytes(const NbDevGraph &g)
-{
-    return align16((size_t)g.N * g.m * 4) + align16((size_t)g.N) + align16((size_t)g.M) +
-           align16((size_t)g.N * 4) + align16((size_t)g.E * 2) + align16((size_t)g.E) +
-           align16((size_t)(g.M + 3) / 4 * 4) + (16 * 3 + 16 + 4 + 4) * 4;
-}
-
-template <int Q, int MB, int DC, int SRC, bool GSTATE, int THREADS>
+// offsets are its ds addresses as they are, without an add per entry). SCHED_LDS = false
+// (ems_global_sched, GSTATE only) leaves out cn_d, vn, vslot and vh: the schedule is read
+// from its packed device copy (NbDevSched) through the caches, where those four
+// tables and the per-codeword state together exceed LDS (nb_layout.h nb_plan).
+template <int Q, int MB, int DC, int SRC, bool GSTATE, int THREADS, bool SCHED_LDS = true>
 __global__ __launch_bounds__(THREADS) void k_ems(NbArgs a, NbDevGraph g, float *gscratch,
-                                                            size_t slot_floats)
+                                                            size_t slot_floats, NbDevSched ds)
 {
+    static_assert(SCHED_LDS || GSTATE, "the schedule leaves LDS after the messages");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int Ep = nb_ep(g);
     unsigned char *p = smem;
@@ -693,32 +708,37 @@ __global__ __launch_bounds__(THREADS) void k_ems(NbArgs a, NbDevGraph g, float *
         msg = gscratch + slot_floats * blockIdx.x;
     } else {
         msg = reinterpret_cast<float *>(p);
-        p += align16((size_t)Ep * Q * 4);
+        p += nb_align16((size_t)Ep * Q * 4);
     }
     float *lam = reinterpret_cast<float *>(p);
-    p += align16((size_t)g.N * MB * 4);
+    p += nb_align16((size_t)g.N * MB * 4);
     uint8_t *dec = p;
-    p += align16((size_t)g.N);
-    uint8_t *cn_d = p;
-    p += align16((size_t)g.M);
-    uint32_t *vn = reinterpret_cast<uint32_t *>(p);
-    p += align16((size_t)g.N * 4);
-    uint16_t *vslot = reinterpret_cast<uint16_t *>(p);
-    p += align16((size_t)g.E * 2);
-    uint8_t *vh = p;
-    p += align16((size_t)g.E);
+    p += nb_align16((size_t)g.N);
+    [[maybe_unused]] uint8_t *l_cn_d = p;   // the schedule's LDS copy (SCHED_LDS)
+    if (SCHED_LDS) p += nb_align16((size_t)g.M);
+    [[maybe_unused]] uint32_t *l_vn = reinterpret_cast<uint32_t *>(p);
+    if (SCHED_LDS) p += nb_align16((size_t)g.N * 4);
+    [[maybe_unused]] uint16_t *l_vslot = reinterpret_cast<uint16_t *>(p);
+    if (SCHED_LDS) p += nb_align16((size_t)g.E * 2);
+    [[maybe_unused]] uint8_t *l_vh = p;
+    if (SCHED_LDS) p += nb_align16((size_t)g.E);
     uint32_t *synd = reinterpret_cast<uint32_t *>(p);   // check j: byte j & 3 of word j >> 2
-    p += align16((size_t)(g.M + 3) / 4 * 4);
+    p += nb_align16((size_t)(g.M + 3) / 4 * 4);
     int *red = reinterpret_cast<int *>(p);   // [48, 64) wave flags, [64] the ticket, [65, 68) the block totals
     for (int w = threadIdx.x; w < (g.M + 3) / 4; w += blockDim.x) synd[w] = 0u;
     if (threadIdx.x < 3) red[65 + threadIdx.x] = 0;   // the block totals (ems_codeword)
-    for (int j = threadIdx.x; j < g.M; j += blockDim.x) cn_d[j] = (uint8_t)(g.row_ptr[j + 1] - g.row_ptr[j]);
-    for (int v = threadIdx.x; v < g.N; v += blockDim.x)
-        vn[v] = ((uint32_t)g.col_ptr[v] << 8) | (uint32_t)(g.col_ptr[v + 1] - g.col_ptr[v]);
-    for (int e = threadIdx.x; e < g.E; e += blockDim.x) {
-        vslot[e] = (uint16_t)g.col_pslot[e];
-        vh[e] = g.col_h[e];
+    if constexpr (SCHED_LDS) {
+        for (int j = threadIdx.x; j < g.M; j += blockDim.x) l_cn_d[j] = (uint8_t)(g.row_ptr[j + 1] - g.row_ptr[j]);
+        for (int v = threadIdx.x; v < g.N; v += blockDim.x)
+            l_vn[v] = ((uint32_t)g.col_ptr[v] << 8) | (uint32_t)(g.col_ptr[v + 1] - g.col_ptr[v]);
+        for (int e = threadIdx.x; e < g.E; e += blockDim.x) {
+            l_vslot[e] = (uint16_t)g.col_pslot[e];
+            l_vh[e] = g.col_h[e];
+        }
     }
+    const uint8_t *cn_d = SCHED_LDS ? l_cn_d : ds.cn_d, *vh = SCHED_LDS ? l_vh : g.col_h;
+    const uint32_t *vn = SCHED_LDS ? l_vn : ds.vn;
+    const uint16_t *vslot = SCHED_LDS ? l_vslot : ds.vslot;
     __syncthreads();
     const NbSched sc{Ep, g.M, nb_ep_log2(Ep) + 4, cn_d, vn, vslot, vh};
     EmsStamps st;
@@ -746,47 +766,47 @@ __global__ __launch_bounds__(THREADS) void k_ems(NbArgs a, NbDevGraph g, float *
 #endif
 }
 
-constexpr size_t kNbMaxLds = 160 * 1024;
-
 NbChoice nb_choose(const NbDevGraph &g, int maxdc)
 {
     NbChoice ch;
     ch.dc = maxdc <= 4 ? 4 : 8;
-    // DC = 4: 1024 threads (4 waves per SIMD; 128 VGPRs, spills only around
+    // GF(16), DC = 4: 1024 threads (4 waves per SIMD; 128 VGPRs, spills only around
     // the codeword loop: 8.12 vs 8.00 Gbit/s at 2.0 dB with 512),
     // LDPC_OPT_EMS_THREADS = 512 the other build. DC = 8: 512 (its check node needs
     // ~180 VGPRs). LDS allows one workgroup per CU either way.
+    // GF(4) and GF(8): a check lane holds 4 or 8 floats a vector, so both row-degree
+    // builds exist at 512 and at 1024 threads and LDPC_OPT_EMS_THREADS picks either;
+    // the default is what DESIGN §11 measured.
     ch.threads = 512;
-    if (ch.dc == 4) {
+    if (g.q < kNbQ) {
+        ch.threads = kNbThreadsSmallQ;
+        if (opt(LDPC_OPT_EMS_THREADS) == 512 || opt(LDPC_OPT_EMS_THREADS) == 1024) ch.threads = opt(LDPC_OPT_EMS_THREADS);
+    } else if (ch.dc == 4) {
         ch.threads = 1024;
         if (opt(LDPC_OPT_EMS_THREADS) == 512) ch.threads = 512;
     }
-    const size_t aux = aux_bytes(g), msgb = align16((size_t)nb_ep(g) * g.q * 4);
-    // The 16-bit schedule entries are the slot indices (< maxdc * M: vslot) and the
-    // symbols (< N); the chunk stride Ep (maxdc * M rounded up to a power of two, up to
-    // 65 536) only enters int offsets.
-    if (maxdc > kNbMaxDc || aux > kNbMaxLds || (long)g.maxdc * g.M > 65535 || g.N > 65535) {
-        return ch;   // unsupported (ok stays false)
-    }
+    const NbPlan pl = nb_plan(g.N, g.M, g.E, g.q, g.m, maxdc);
+    if (pl.kind == NB_NONE) return ch;   // unsupported (ok stays false)
     ch.ok = true;
-    if (aux + msgb <= kNbMaxLds) {
-        ch.name = "ems_lds";
-        ch.lds_bytes = (int)(aux + msgb);
-    } else {
-        ch.name = "ems_global";
-        ch.lds_bytes = (int)aux;
-        ch.slot_bytes = msgb;
-    }
+    ch.name = pl.kind == NB_LDS ? "ems_lds" : pl.kind == NB_GLOBAL ? "ems_global" : "ems_global_sched";
+    ch.sched_lds = pl.kind != NB_GLOBAL_SCHED;
+    ch.lds_bytes = (int)pl.lds_bytes;
+    ch.slot_bytes = pl.slot_bytes;
     return ch;
 }
 
 LDPC_CHECK_TU(nb)
 
-template <int DC, int SRC, bool GS>
-static hipError_t launch_t(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, void *scratch, int grid,
-                           hipStream_t s)
+// GS: 0 = messages in LDS, 1 = in the global slot, 2 = the schedule read from global memory too.
+template <int Q, int DC, int SRC, int GS>
+static hipError_t launch_t(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, const NbDevSched &ds, void *scratch,
+                           int grid, hipStream_t s)
 {
-    auto fn = (DC == 4 && ch.threads == 1024) ? k_ems<kNbQ, 4, DC, SRC, GS, 1024> : k_ems<kNbQ, 4, DC, SRC, GS, 512>;
+    constexpr int MB = kBitsOf<Q>;
+    // GF(16) at row degree above 4 has the 512-thread build only (nb_choose)
+    constexpr int TBIG = (Q < kNbQ || DC == 4) ? 1024 : 512;
+    auto fn = ch.threads == 1024 ? k_ems<Q, MB, DC, SRC, GS != 0, TBIG, GS != 2> : k_ems<Q, MB, DC, SRC, GS != 0, 512, GS != 2>;
+    if (ch.threads != 512 && ch.threads != TBIG) return hipErrorInvalidValue;
     hipError_t e = hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, ch.lds_bytes);
     if (e != hipSuccess) return e;
     if (!GS) {
@@ -799,27 +819,37 @@ static hipError_t launch_t(const NbDevGraph &g, const NbArgs &a, const NbChoice 
         if (fa.sharedSizeBytes != 0) return hipErrorInvalidDeviceFunction;
     }
     hipLaunchKernelGGL(fn, dim3(grid), dim3(ch.threads), ch.lds_bytes, s, a, g, (float *)scratch,
-                       ch.slot_bytes / 4);
+                       ch.slot_bytes / 4, ds);
     return hipGetLastError();
 }
 
-template <int DC>
-static hipError_t launch_dc(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, void *scratch, int grid,
-                            hipStream_t s)
+template <int Q, int DC>
+static hipError_t launch_dc(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, const NbDevSched &ds, void *scratch,
+                            int grid, hipStream_t s)
 {
-    const bool gs = ch.slot_bytes != 0;
+    const int gs = !ch.slot_bytes ? 0 : ch.sched_lds ? 1 : 2;
     if (a.src == SRC_GIVEN)
-        return gs ? launch_t<DC, SRC_GIVEN, true>(g, a, ch, scratch, grid, s)
-                  : launch_t<DC, SRC_GIVEN, false>(g, a, ch, scratch, grid, s);
-    return gs ? launch_t<DC, SRC_PHILOX, true>(g, a, ch, scratch, grid, s)
-              : launch_t<DC, SRC_PHILOX, false>(g, a, ch, scratch, grid, s);
+        return gs == 0   ? launch_t<Q, DC, SRC_GIVEN, 0>(g, a, ch, ds, scratch, grid, s)
+               : gs == 1 ? launch_t<Q, DC, SRC_GIVEN, 1>(g, a, ch, ds, scratch, grid, s)
+                         : launch_t<Q, DC, SRC_GIVEN, 2>(g, a, ch, ds, scratch, grid, s);
+    return gs == 0   ? launch_t<Q, DC, SRC_PHILOX, 0>(g, a, ch, ds, scratch, grid, s)
+           : gs == 1 ? launch_t<Q, DC, SRC_PHILOX, 1>(g, a, ch, ds, scratch, grid, s)
+                     : launch_t<Q, DC, SRC_PHILOX, 2>(g, a, ch, ds, scratch, grid, s);
 }
 
-hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, void *scratch, int slots,
-                     int num_cus, hipStream_t s)
+template <int Q>
+static hipError_t launch_q(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, const NbDevSched &ds, void *scratch,
+                           int grid, hipStream_t s)
+{
+    return ch.dc == 4 ? launch_dc<Q, 4>(g, a, ch, ds, scratch, grid, s) : launch_dc<Q, 8>(g, a, ch, ds, scratch, grid, s);
+}
+
+hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, const NbDevSched &ds, void *scratch,
+                     int slots, int num_cus, hipStream_t s)
 {
     if (a.batch <= 0) return hipSuccess;
-    if (g.q != kNbQ || g.m != 4 || !ch.ok) return hipErrorInvalidValue;
+    if (!nb_q_supported(g.q) || (1 << g.m) != g.q || !ch.ok) return hipErrorInvalidValue;
+    if (!ch.sched_lds && (!ds.cn_d || !ds.vn || !ds.vslot)) return hipErrorInvalidValue;
     int grid;
     if (ch.slot_bytes) {
         if (!scratch || slots <= 0) return hipErrorInvalidValue;
@@ -843,8 +873,9 @@ hipError_t nb_launch(const NbDevGraph &g, const NbArgs &a, const NbChoice &ch, v
         const hipError_t e = hipMemsetAsync(a.ticket, 0, sizeof(unsigned), s);
         if (e != hipSuccess) return e;
     }
-    const hipError_t err =
-        ch.dc == 4 ? launch_dc<4>(g, a, ch, scratch, grid, s) : launch_dc<8>(g, a, ch, scratch, grid, s);
+    const hipError_t err = g.q == 4   ? launch_q<4>(g, a, ch, ds, scratch, grid, s)
+                           : g.q == 8 ? launch_q<8>(g, a, ch, ds, scratch, grid, s)
+                                      : launch_q<16>(g, a, ch, ds, scratch, grid, s);
 #ifdef LDPC_EMS_STAMPS
     if (stamp_path && err == hipSuccess) {
         static unsigned long long h[kEmsStampBlocks * 16 * 8];

@@ -26,6 +26,7 @@ struct ldpc_nb_ctx : CtxCore {
     ldpc::NbDevGraph dg{};
     DevBuf graph, y_stage, c_stage, d_stage, fr_stage, scratch;
     const uint8_t *col_h_swz = nullptr;   // device: col_h with the slot swizzles (nb_swizzled_coefficients)
+    ldpc::NbDevSched ds{};                // device: the packed schedule (ems_global_sched reads it in place)
 };
 
 // LDPC_OPT_EMS_SWIZZLE = 1 keeps the plain message layout (A/B).
@@ -93,12 +94,14 @@ static int nb_ctx_init(ldpc_nb_ctx *c, int device, const ldpc_nb_graph *g, int m
     c->g = g;
     RC_TRY(c->init(device, max_batch));
     // graph upload: row_ptr | row_col | col_ptr | col_slot | row_h | gf_mul | gf_inv | pslot | colh | colh_swz
+    //               | cn_d | vn | vslot
     ldpc::NbTables tb;
     ldpc::nb_tables(*g, tb);
     Blob b(16);
     const size_t o_rp = b.add(g->row_ptr), o_rc = b.add(g->row_col), o_cp = b.add(g->col_ptr),
                  o_cs = b.add(g->col_slot), o_h = b.add(g->row_h), o_mul = b.add(tb.mul), o_inv = b.add(tb.inv),
-                 o_ps = b.add(tb.pslot), o_ch = b.add(tb.colh), o_chs = b.add(tb.colh_swz);
+                 o_ps = b.add(tb.pslot), o_ch = b.add(tb.colh), o_chs = b.add(tb.colh_swz),
+                 o_cd = b.add(tb.cn_d), o_vn = b.add(tb.vn), o_vs = b.add(tb.vslot);
     HIP_TRY(upload(b, c->graph));
     const auto *base = (const uint8_t *)c->graph.p;
     c->dg.N = g->N;
@@ -116,9 +119,13 @@ static int nb_ctx_init(ldpc_nb_ctx *c, int device, const ldpc_nb_graph *g, int m
     c->dg.col_pslot = (const int32_t *)(base + o_ps);
     c->dg.col_h = base + o_ch;
     c->col_h_swz = base + o_chs;
+    c->ds.cn_d = base + o_cd;
+    c->ds.vn = (const uint32_t *)(base + o_vn);
+    c->ds.vslot = (const uint16_t *)(base + o_vs);
     c->dg.maxdc = g->maxdc;
     if (!ldpc::nb_choose(c->dg, g->maxdc).ok)
-        return set_err(LDPC_ERR_UNSUPPORTED, "code too large for the EMS kernels (N=%d, E=%d)", g->N, g->E);
+        return set_err(LDPC_ERR_UNSUPPORTED, "code too large for the EMS kernels (N=%d, M=%d, E=%d, q=%d)", g->N, g->M,
+                       g->E, g->q);
     return LDPC_OK;
 }
 
@@ -127,7 +134,9 @@ int ldpc_nb_ctx_create(int device, const ldpc_nb_graph *g, int max_batch, ldpc_n
     if (!g || !out) return set_err(LDPC_ERR_INVALID, "null argument");
     *out = nullptr;
     if (max_batch <= 0) return set_err(LDPC_ERR_INVALID, "max_batch must be > 0");
-    if (g->q != ldpc::kNbQ) return set_err(LDPC_ERR_UNSUPPORTED, "the EMS kernels are built for GF(16), got q=%d", g->q);
+    if (!ldpc::nb_q_supported(g->q))
+        return set_err(LDPC_ERR_UNSUPPORTED, "the EMS kernels are built for GF(4), GF(8) and GF(16), got q=%d (%s)", g->q,
+                       g->q == 2 ? "binary codes have their own decoders" : "its check lanes would not hold their vectors");
     if (g->maxdc > ldpc::kNbMaxDc) return set_err(LDPC_ERR_UNSUPPORTED, "row degree %d > %d", g->maxdc, ldpc::kNbMaxDc);
     if (g->maxdv > 255) return set_err(LDPC_ERR_UNSUPPORTED, "column degree %d > 255", g->maxdv);
     int ndev = 0;
@@ -175,7 +184,7 @@ static int run(ldpc_nb_ctx *c, const ldpc::NbArgs &a)
     // entries by symbol on ties, so it keeps the plain one (nb.hip vn_lane)
     if (a.nm >= dg.q && nb_swizzle_enabled()) dg.col_h = c->col_h_swz;
     return run_with_slots(*c, c->scratch, ch, a.batch, c->num_cus, [&](void *scratch, int slots) {
-        return ldpc::nb_launch(dg, a, ch, scratch, slots, c->num_cus, c->stream);
+        return ldpc::nb_launch(dg, a, ch, c->ds, scratch, slots, c->num_cus, c->stream);
     });
 }
 

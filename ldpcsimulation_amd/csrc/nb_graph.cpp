@@ -60,6 +60,10 @@ int gf_mul(int q, int a, int b)
 // the LDS bank model of the gathers: two groups of 32 lanes, bank = dword mod
 // 32, cost = the most-used bank. Moves XOR the same delta into two slots of one
 // check. Deterministic (fixed seed). Returned: col_h | f << 4 per column entry.
+// GF(16) only: for GF(4) and GF(8) f stays 0 (the plain layout). The search's bank model
+// and its gain were measured on the LDS-resident GF(16) code; both reference codes of the
+// smaller fields keep their messages in global memory, where LDS banks do not enter, and
+// nothing was measured that would justify a search there. The kernels take any f.
 std::vector<uint8_t> nb_swizzled_coefficients(const ldpc_nb_graph &g, const std::vector<int32_t> &pslot,
                                                      const std::vector<uint8_t> &colh, const std::vector<uint8_t> &mul)
 {
@@ -231,6 +235,13 @@ void nb_tables(const ldpc_nb_graph &g, NbTables &t)
                     t.colh[e] = g.row_h[r];
                 }
     t.colh_swz = nb_swizzled_coefficients(g, t.pslot, t.colh, t.mul);
+    t.cn_d.assign(g.M, 0);
+    t.vn.assign(g.N, 0);
+    t.vslot.assign(g.E, 0);
+    for (int j = 0; j < g.M; ++j) t.cn_d[j] = (uint8_t)(g.row_ptr[j + 1] - g.row_ptr[j]);
+    for (int v = 0; v < g.N; ++v)
+        t.vn[v] = ((uint32_t)g.col_ptr[v] << 8) | (uint32_t)(g.col_ptr[v + 1] - g.col_ptr[v]);
+    for (int e = 0; e < g.E; ++e) t.vslot[e] = t.pslot[e] < 65536 ? (uint16_t)t.pslot[e] : 0;
 }
 
 }  // namespace ldpc

@@ -34,6 +34,10 @@ struct NbTables {
     std::vector<int32_t> pslot;        // [E] column entry -> position-major slot k*M + j
     std::vector<uint8_t> colh;         // [E] its coefficient
     std::vector<uint8_t> colh_swz;     // [E] coefficient | slot XOR swizzle << 4 (GF(16) only; else = colh)
+    // the schedule as k_ems packs it (nb.h NbDevSched), for the instance that reads it from global memory
+    std::vector<uint8_t> cn_d;         // [M] check degree
+    std::vector<uint32_t> vn;          // [N] first column entry << 8 | degree
+    std::vector<uint16_t> vslot;       // [E] pslot in 16 bits (0 where a slot does not fit: such graphs get no kernel)
 };
 void nb_tables(const ldpc_nb_graph &g, NbTables &t);
 std::vector<uint8_t> nb_swizzled_coefficients(const ldpc_nb_graph &g, const std::vector<int32_t> &pslot,

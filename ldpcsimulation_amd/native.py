@@ -1026,7 +1026,8 @@ class NbGraph:
 
 
 class NbContext:
-    """Device context of the EMS decoder (GF(16))."""
+    """Device context of the EMS decoder: GF(4), GF(8) and GF(16) graphs (other q:
+    LdpcError, LDPC_ERR_UNSUPPORTED). A symbol is m = log2(q) channel samples."""
 
     def __init__(self, graph: NbGraph, device: int = 0, max_batch: int = 65536):
         self.graph = graph
@@ -1049,15 +1050,23 @@ class NbContext:
         _check(lib().ldpc_nb_ctx_set_option(self._h, option_id(name), option_value(name, value)))
 
     def decode(self, y, n0: float, cfg: EmsConfig, c=None, want_decisions: bool = True):
-        """Decode y[batch, N*m] float32 (numpy or torch, host or device). Returns (d [batch,N] uint8, frames, NbCounts)."""
+        """Decode y[batch, N*m] float32 (numpy or torch, host or device), m = log2(q) samples per symbol,
+        bit i of a symbol at column v*m + i. A y of another width is a ValueError. Returns
+        (d [batch,N] uint8, frames, NbCounts)."""
         g = self.graph
+        width = g.N * g.m
         if isinstance(y, np.ndarray):
             if y.dtype != np.float32:
                 raise TypeError(f"y must be float32, got {y.dtype}")
             y = np.ascontiguousarray(y)
-            batch = y.size // (g.N * g.m)
+            size, shape = y.size, y.shape
         else:
-            batch = y.numel() // (g.N * g.m)
+            size, shape = y.numel(), tuple(y.shape)
+        if size == 0 or size % width or (len(shape) > 1 and shape[-1] != width):
+            raise ValueError(f"y must be [batch, N*m = {width}] (GF({g.q}): {g.m} samples per symbol), got {shape}")
+        batch = size // width
+        if c is not None and tuple(c.shape) != (batch, g.N):
+            raise ValueError(f"c must be [batch, N] = {(batch, g.N)}, got {tuple(c.shape)}")
         if c is not None and isinstance(c, np.ndarray):
             c = np.ascontiguousarray(c, dtype=np.uint8)
         d = np.empty((batch, g.N), dtype=np.uint8) if want_decisions else None
@@ -1078,6 +1087,8 @@ class NbContext:
 
     def sim_trace(self, ebn0_db: float, R: float, cfg: EmsConfig, seed: int, stream_id: int, first_cw: int,
                   batch: int):
+        """sim_batch that also returns the generated samples y [batch, N*m] (symbol v's bits 0..m-1 at
+        columns v*m .. v*m + m - 1) and the decisions d [batch, N]."""
         g = self.graph
         y = np.empty((batch, g.N * g.m), dtype=np.float32)
         d = np.empty((batch, g.N), dtype=np.uint8)

@@ -88,6 +88,11 @@ CONFIGS = {
                            what="config 4: SMNGDBF on 802.11n N=1944, T<=100, fp64"),
     "c5_ems_gf16": dict(kind="ems", T=20, nm=16, batch=16384, snr=2.0,
                         what="config 5: GF(16) EMS, N=1000 symbols (4000 bits), nm=16, T<=20"),
+    # the reference's own non-binary codes (SystemC/NB-LDPC/codes/GF4, GF8), full vectors
+    "ems_ref_gf4": dict(kind="ems", code="q4.sp.9000.6000.4500.1.alist", T=20, nm=4, batch=16384, snr=2.0, rate=0.3333,
+                        what="GF(4) EMS on the reference's q4.sp.9000.6000 (18000 bits), nm=4, T<=20"),
+    "ems_ref_gf8": dict(kind="ems", code="q8.sp.6000.4000.3000.1.alist", T=20, nm=8, batch=16384, snr=2.0, rate=0.3333,
+                        what="GF(8) EMS on the reference's q8.sp.6000.4000 (18000 bits), nm=8, T<=20"),
     "bp_80211n_f64": dict(kind="minsum", code="80211n_1944_r12.alist", variant="bp", prec="f64", T=50,
                           batch=16384, snr=1.5, what="BP (tanh rule) on 802.11n N=1944, T=50, fp64"),
     "bp_80211n_f32": dict(kind="minsum", code="80211n_1944_r12.alist", variant="bp", prec="f32", T=50,
@@ -210,7 +215,7 @@ class Workload:
         self.native, self.name, self.c = native, name, CONFIGS[name]
         c = self.c
         if c["kind"] == "ems":
-            self.g = native.NbGraph.from_alist(codes.ensure_gf16_code())
+            self.g = native.NbGraph.from_alist(code_path(c["code"]) if "code" in c else codes.ensure_gf16_code())
             self.ctx = native.NbContext(self.g, 0, c["batch"])
             self.cfg = native.EmsConfig(T=c["T"], nm=c["nm"], offset=0.0, early_stop=True)
             self.bits = self.g.N * self.g.m
